@@ -16,9 +16,18 @@ scaling weak: every rank grids its own 64 channels; the N-GPU job is the same
         array observed in 64*N channels interleaved over 0.95-1.76 GHz, so
         every shard has the same uv extent and w-plane count.
 
-Rank 0 prints ONE JSON line.  With --gpus 1 (the default) and the default
-config it also carries one object per other configuration, each with its own
-steps, timing, `roofline` and `cpu_baseline` (--no-extra skips them):
+Rank 0 prints ONE JSON line.  A plain run (`--gpus 1 --steps N --warmup W`)
+sets up, warms up, times the N steps and prints the headline: metric, value,
+unit, higher_is_better, dtype, ms_per_step and the workload's config.
+--dump-outputs DIR also writes what the last timed step returned (the dirty
+image and the weight sum) as DIR/<name>.npy; the inputs are seeded, so two
+builds can be compared output for output.
+
+--full adds everything that takes runs of its own: a serial pass with stage
+timing (`stages_ms`, `roofline`, the serial step time), `cpu_baseline`, the
+`api` timings, and, with --gpus 1 and the default config, one object per other
+configuration, each with its own steps, timing, `roofline` and `cpu_baseline`
+(--no-extra skips them):
   "c4_n1"  configs[3] at N = 1: the whole 256-channel SKA-LOW band (13.4 Gvis,
            8192^2 image, 16384^2 grid, 71 w planes) streamed through
            sdp_hip_ms2dirty_batch -- the metric's own 8k^2 configuration;
@@ -55,6 +64,33 @@ F_LO, F_HI = 0.95e9, 1.76e9
 EPS_REQUESTED = 1e-7  # the fp32 NUFFT, W = 8 (epsilon < 1e-7 selects fp64)
 EPS_REFERENCE = 1e-12  # invert_ng's default (ng.py:178): the fp64 NUFFT, W = 13
 FP64_PEAK_TFLOPS = 78.6       # fp64 vector = fp64 matrix peak on gfx950
+DUMP_MAX_ELEMS = 4_000_000    # --dump-outputs: elements per array (32 MB as f64)
+DUMP_MAX_BYTES = 64_000_000   # --dump-outputs: all arrays together
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every tensor of `arrays` as directory/<name>.npy, in
+    float32 or float64 (other real dtypes as float64, complex as a trailing
+    [re, im] axis).  An array of more than DUMP_MAX_ELEMS elements is written
+    as a sample of its flattened elements at sorted indices drawn from a
+    generator seeded by the element count alone, so the same positions are
+    sampled in every run of the same shape."""
+    os.makedirs(directory, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.is_complex():
+            t = torch.view_as_real(t.resolve_conj())
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.to(torch.float64)
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(t.numel()).integers(0, t.numel(), DUMP_MAX_ELEMS))
+            t = t.reshape(-1)[torch.as_tensor(idx, device=t.device)]
+        a = t.cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_MAX_BYTES} bytes")
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def parse():
@@ -65,10 +101,20 @@ def parse():
     ap.add_argument("--nchan", type=int, default=NCHAN_PER_GPU, help="channels per GPU")
     ap.add_argument("--ntimes", type=int, default=NTIMES)
     ap.add_argument("--npix", type=int, default=NPIX)
+    ap.add_argument("--full", action="store_true",
+                    help="default config: after the timed steps also run the serial stage-timed "
+                         "pass (stages_ms, roofline), the cpu_baseline, the api timings and the "
+                         "c2_predict / c2_fp64 / c4_n1 / c3 / c5 objects (see --cpu-chans, "
+                         "--no-api, --no-extra); off: only the headline measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them returned as "
+                         "DIR/<name>.npy (float32 / float64; complex as trailing [re, im]; an "
+                         f"array of more than {DUMP_MAX_ELEMS} elements as a fixed seeded "
+                         "sample of its flattened elements); configs c2, c3 and c4")
     ap.add_argument("--cpu-chans", type=int, default=8,
-                    help="channels in the cpu_baseline sample (0 = skip)")
+                    help="--full: channels in the cpu_baseline sample (0 = skip)")
     ap.add_argument("--no-api", action="store_true",
-                    help="skip the invert_ng API (device / host Visibility) timings")
+                    help="--full: skip the invert_ng API (device / host Visibility) timings")
     ap.add_argument("--traffic", default=os.path.join(ROOT, "profiles", "traffic_k_grid.json"))
     ap.add_argument("--config", choices=("c2", "c3", "c4", "c5"), default="c2",
                     help="c2: configs[1], weak scaling (default); c3: configs[2], the sky-"
@@ -93,7 +139,7 @@ def parse():
                     help="c2: run the steps back to back on one stream (default: two streams "
                          "and two library scratch slots, consecutive inverts overlapping)")
     ap.add_argument("--no-extra", action="store_true",
-                    help="default config at N=1: skip the c4_n1 / c3 / c5 objects")
+                    help="--full, default config at N=1: skip the c4_n1 / c3 / c5 objects")
     ap.add_argument("--extra-steps", type=int, default=2,
                     help="timed steps of the c4_n1 and c5 objects (c3 uses --steps)")
     ap.add_argument("--c4-cpu-chans", type=int, default=2,
@@ -119,7 +165,12 @@ def parse():
     ap.add_argument("--emulate", default=None, metavar="RANK/WORLD",
                     help="c4 on one GPU: run only rank RANK's block of a WORLD-way partition "
                          "(no collective), to measure per-rank times")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.config == "c5" or args.c4_api or args.emulate):
+        ap.error("--dump-outputs: not with --config c5, --c4-api or --emulate")
+    return args
 
 
 def cpu_baseline(args, umax, nchan_total):
@@ -637,6 +688,8 @@ def run_c4(args, world, rank, local, dev, emulated=False, sub=False):
                 reduce()
         barrier()
         elapsed = seg["t"]
+    if args.dump_outputs and rank == 0 and not sub:
+        dump_outputs(args.dump_outputs, {"dirty": out})
     # one extra, untimed pass with stage timing for the kernel breakdown
     kernels.set_stage_timing(True)
     orig = kernels.ms2dirty_batch
@@ -928,6 +981,8 @@ def run_c3(args, world, rank, dev, sub=False):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     ms_step = elapsed / args.steps * 1e3
+    if args.dump_outputs and not sub:  # (each rank its own rows)
+        dump_outputs(args.dump_outputs, {"vis" if world == 1 else f"vis_rank{rank}": out})
     if rank != 0:
         return
     flops = (hi - lo) * C3_NCOMP * (6 + 8 * 1)
@@ -1204,14 +1259,14 @@ def main():
         j = i % len(streams) if pipelined else 0
 
         def run():
-            parallel.invert_sharded(obs["uvw"], obs["freq"], obs["vis"], obs["wgt"], args.npix,
-                                    cell, EPS_REQUESTED, True, flip_uw=True, normalise=True,
-                                    grid_fn=grid_fn_slot(j), out=outs[j], fused_sumwt=fused_sw)
+            return parallel.invert_sharded(obs["uvw"], obs["freq"], obs["vis"], obs["wgt"],
+                                           args.npix, cell, EPS_REQUESTED, True, flip_uw=True,
+                                           normalise=True, grid_fn=grid_fn_slot(j), out=outs[j],
+                                           fused_sumwt=fused_sw)
         if streams[j] is None or not pipelined:  # (serial: the whole GPU, default stream)
-            run()
-        else:
-            with torch.cuda.stream(streams[j]):
-                run()
+            return run()
+        with torch.cuda.stream(streams[j]):
+            return run()
 
     def barrier():
         if world > 1:
@@ -1227,28 +1282,57 @@ def main():
         barrier()
         t0 = time.perf_counter()
         for i in range(args.steps):
-            step(i, pipelined)
+            last = step(i, pipelined)
         barrier()
         el = time.perf_counter() - t0
         if world > 1:
             t = torch.tensor([el], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
-        return el
+        return el, last
 
-    elapsed = timed(pipe)
-    # the gridder's launch duration: a serial pass (one stream) with stage
+    infos.clear()
+    elapsed, (dirty, sumwt) = timed(pipe)
+    info = infos[-1]
+    ms_step = elapsed / args.steps * 1e3
+    value = nvis_rank * world / (elapsed / args.steps) / 1e6
+    if args.dump_outputs and rank == 0:  # (all-reduced: the same on every rank)
+        dump_outputs(args.dump_outputs, {"dirty": dirty, "sumwt": sumwt})
+    line = {
+        "metric": METRIC, "value": round(value, 3), "unit": "Mvis/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+        "data": "synthetic (seeded SKA-MID-like layout, N(0,1) c64 vis, unit f32 weights, "
+                "generated on device)",
+        "config": {"workload": "C2: SKA-MID 197 dishes, 64 chan x 100 times per GPU, "
+                               f"{args.npix}^2 image, {info['ngrid_x']}^2 w-stack grid",
+                   "pipelined": ("consecutive inverts on two streams / library scratch "
+                                 "slots: step i+1's bucketing under step i's gridding + "
+                                 "FFT" + (f"; streams on disjoint CU masks ({args.cu_split})"
+                                          if args.cu_split else "") if pipe else False),
+                   "nvis_per_gpu": nvis_rank, "nchan_total": nchan_total,
+                   "npix": args.npix, "cell_rad": cell, "support": info["support"],
+                   "nplanes": info["nplanes"], "epsilon_requested": EPS_REQUESTED,
+                   "parallelism": f"channel-sharded x{world}, 1 all-reduce"},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    del dirty, sumwt
+
+    # --full: the gridder's launch duration: a serial pass (one stream) with stage
     # timing on -- the C ABI brackets k_grid with HIP events on its launch
     # stream, which synchronises the host after each call, so it is not the
     # timed (overlapped) loop
     kernels.set_stage_timing(True)
     infos.clear()
-    elapsed_serial = timed(False)
+    elapsed_serial, _ = timed(False)
     kernels.set_stage_timing(False)
 
     info = infos[-1]
-    ms_step = elapsed / args.steps * 1e3
-    value = nvis_rank * world / (elapsed / args.steps) / 1e6
     ms_grid = float(np.mean([i["ms_grid"] for i in infos]))
     launches = max(1, info["grid_launches"])
     alg_bytes = nvis_rank * (8 + 4 + 24.0 / len(chans)) + \
@@ -1308,31 +1392,15 @@ def main():
         torch.cuda.empty_cache()
 
     if rank == 0:
-        line = {
-            "metric": METRIC, "value": round(value, 3), "unit": "Mvis/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic (seeded SKA-MID-like layout, N(0,1) c64 vis, unit f32 weights, "
-                    "generated on device)",
-            "config": {"workload": "C2: SKA-MID 197 dishes, 64 chan x 100 times per GPU, "
-                                   f"{args.npix}^2 image, {info['ngrid_x']}^2 w-stack grid",
-                       "pipelined": ("consecutive inverts on two streams / library scratch "
-                                     "slots: step i+1's bucketing under step i's gridding + "
-                                     "FFT" + (f"; streams on disjoint CU masks ({args.cu_split})"
-                                              if args.cu_split else "") if pipe else False),
-                       "ms_per_step_serial": round(elapsed_serial / args.steps * 1e3, 3),
-                       "value_serial": round(nvis_rank * world / (elapsed_serial / args.steps)
-                                             / 1e6, 3),
-                       "nvis_per_gpu": nvis_rank, "nchan_total": nchan_total,
-                       "npix": args.npix, "cell_rad": cell, "support": info["support"],
-                       "nplanes": info["nplanes"], "epsilon_requested": EPS_REQUESTED,
-                       "parallelism": f"channel-sharded x{world}, 1 all-reduce"},
+        line["config"].update({
+            "ms_per_step_serial": round(elapsed_serial / args.steps * 1e3, 3),
+            "value_serial": round(nvis_rank * world / (elapsed_serial / args.steps) / 1e6, 3)})
+        line.update({
             "stages_ms": {k: round(float(np.mean([i[k] for i in infos])), 3)
                           for k in ("ms_prep", "ms_grid", "ms_fft", "ms_screen")},
             "roofline": roof,
             "cpu_baseline": cpu,
-            "api": api,
-        }
+            "api": api})
         line.update(extra)
         print(json.dumps(line), flush=True)
     if world > 1:

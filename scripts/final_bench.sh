@@ -1,6 +1,9 @@
 #!/bin/bash
-# the default bench line on the current build -> gpurun_out/bench_final.json
+# the full bench line (bench.py --full) on the current build -> OUT/bench_final.json
+# (OUT: first argument, default bench_out)
 cd "$(dirname "$0")/.." || exit 1
-timeout -k 10 1000 python3 bench.py > gpurun_out/bench_final.json 2> gpurun_out/bench_final.err; rc=$?
-tail -3 gpurun_out/bench_final.err
+out=${1:-bench_out}
+mkdir -p "$out"
+timeout -k 10 1000 python3 bench.py --full > "$out/bench_final.json" 2> "$out/bench_final.err"; rc=$?
+tail -3 "$out/bench_final.err"
 exit $rc

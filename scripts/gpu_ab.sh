@@ -11,7 +11,7 @@ for r in $(seq 1 $R); do
     lib=${parts[0]}
     envs=("${parts[@]:1}")
     if [ "$lib" = cur ]; then L=""; else L="SDP_HIP_LIB_OVERRIDE=$lib"; fi
-    out=$(env $L "${envs[@]}" timeout -k 10 200 python3 bench.py --steps 20 --warmup 5 --no-extra --no-api --cpu-chans 0 2>/dev/null) || { echo "FAILED $spec"; exit 1; }
+    out=$(env $L "${envs[@]}" timeout -k 10 200 python3 bench.py --full --steps 20 --warmup 5 --no-extra --no-api --cpu-chans 0 2>/dev/null) || { echo "FAILED $spec"; exit 1; }
     echo "$out" | python3 -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$spec', d['value'], d['ms_per_step'], d['stages_ms'], d['roofline']['kernel_ms'])"
   done
 done

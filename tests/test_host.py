@@ -304,3 +304,30 @@ def test_groupby_time_skips_non_finite_times():
     for t, g in groups:
         np.testing.assert_array_equal(np.asarray(g.vis.data)[:, :, 0, 0],
                                       np.arange(nt * nb).reshape(nt, nb)[rows[t]])
+
+
+def test_bench_dump_outputs_writes_seeded_float_arrays(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float .npy files; a large array is the same
+    sorted sample of its flattened elements in every run; complex arrays get
+    a trailing [re, im] axis; the size limit holds."""
+    import importlib.util
+    import torch
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 1000)
+    img = torch.arange(64 * 64, dtype=torch.float64).reshape(64, 64)
+    vis = torch.complex(torch.arange(5.0), -torch.arange(5.0))
+    arrays = {"dirty": img, "sumwt": torch.tensor([3.0], dtype=torch.float64), "vis": vis}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in arrays}
+    assert a["dirty"].dtype == np.float64 and a["dirty"].shape == (1000,)
+    assert np.all(np.diff(a["dirty"]) >= 0) and len(np.unique(a["dirty"])) > 800
+    assert np.array_equal(a["dirty"], np.load(tmp_path / "b" / "dirty.npy"))
+    assert a["sumwt"].tolist() == [3.0]
+    assert a["vis"].dtype == np.float32 and a["vis"].shape == (5, 2)
+    assert np.array_equal(a["vis"][:, 1], -np.arange(5.0))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 100)
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(str(tmp_path / "c"), {"dirty": img})
