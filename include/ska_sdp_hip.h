@@ -99,6 +99,10 @@ typedef struct sdp_hip_wgrid_info {
     int fp64;             /* the fp64 NUFFT ran (epsilon < 1e-7)            */
     int tiled;            /* one-cell buckets from the two-level (64x64-cell
                              bin, then cell) LDS-histogram sort             */
+    int folded;           /* invert: the visibilities with u < 0 were gridded
+                             as their Hermitian mirrors (-u, -v, -w, conj), so
+                             the plane passes ran over half the row band
+                             (SDP_HIP_HFOLD=0 switches it off)              */
 } sdp_hip_wgrid_info;
 
 /* Library/ABI version and a device probe. */

@@ -101,6 +101,12 @@ struct Geo {
     // slab subtracts its first plane as an integer, so slabs partition the
     // visibilities exactly) -- no fp64 division per visibility
     double kax, kby, kpw, kpw0;
+    // Hermitian fold (invert only, plan_geometry): a visibility with
+    // su * u < 0 is gridded at (-u, -v, -w) with its value conjugated -- the
+    // same real part of the image -- so every footprint lies in the grid rows
+    // from ngx / 2 - W / 2 - 1 up and the plane passes run over half the band.
+    // The plane layout (w0, dw, nplanes, nps) is that of the unfolded w range.
+    int fold;
 };
 
 struct __attribute__((aligned(32))) VisRec {
@@ -184,6 +190,7 @@ struct Coord {
     double w;  // w in wavelengths (sign applied)
     bool ok;
     bool skip = false;  // w slab: inside the sequence's layout, outside this slab
+    bool conj = false;  // folded (Geo::fold): the record holds the value's conjugate
 };
 
 // the visibility's grid coordinates from its row's uvw (metres) and its
@@ -191,10 +198,19 @@ struct Coord {
 __device__ __forceinline__ Coord vis_coord_v(const Geo &g, double um, double vm, double wm,
                                              double s) {
     Coord c;
-    const double ws = wm * s;
+    double ws = wm * s;
+    // (the ORIGINAL w: the writers rotate by the original coordinates' phase
+    // and conjugate the rotated value)
     c.w = g.su * ws;
-    const double a = (um * s) * g.kax;
-    const double b = (vm * s) * g.kby;
+    double a = (um * s) * g.kax;
+    double b = (vm * s) * g.kby;
+    // the fold's one predicate (k_bounds uses the same): u = 0 does not fold
+    if (g.fold && g.su * um < 0.0) {
+        a = -a;
+        b = -b;
+        ws = -ws;
+        c.conj = true;
+    }
     c.ok = fabs(a) < (double)g.ngx && fabs(b) < (double)g.ngy;
     if (!c.ok) return c;
     const double fa = floor(a - 0.5 * g.W), fb = floor(b - 0.5 * g.W);
@@ -290,13 +306,14 @@ __device__ __forceinline__ unsigned coord_key(const Geo &g, const Coord &c, int6
 // uvw extent: per-block partials (no atomics), reduced by one block after
 constexpr int kBoundsBlocks = 1024;
 
-// raw extremes in metres (min/max of su*w, max |u|, max |v|); the host
+// raw extremes in metres (min/max of su*w, max |u|, max |v|, and min/max of
+// the Hermitian-folded su*w: negated on the rows with su*u < 0); the host
 // scales them by the frequency range (w*s is monotonic in w for s > 0)
 __global__ __launch_bounds__(256) void k_bounds(const double *__restrict__ uvw, int64_t rs,
                                                 int64_t nrow, double su,
                                                 double *__restrict__ part) {
-    __shared__ double red[4][4];
-    double wmn = 1e300, wmx = -1e300, umx = 0.0, vmx = 0.0;
+    __shared__ double red[6][4];
+    double wmn = 1e300, wmx = -1e300, umx = 0.0, vmx = 0.0, fmn = 1e300, fmx = -1e300;
     for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < nrow;
          r += (int64_t)gridDim.x * blockDim.x) {
         const double u = uvw[r * rs], v = uvw[r * rs + 1], w = su * uvw[r * rs + 2];
@@ -304,12 +321,17 @@ __global__ __launch_bounds__(256) void k_bounds(const double *__restrict__ uvw, 
         wmx = fmax(wmx, w);
         umx = fmax(umx, fabs(u));
         vmx = fmax(vmx, fabs(v));
+        const double wf = su * u < 0.0 ? -w : w;
+        fmn = fmin(fmn, wf);
+        fmx = fmax(fmx, wf);
     }
     for (int o = 32; o > 0; o >>= 1) {
         wmn = fmin(wmn, __shfl_xor(wmn, o));
         wmx = fmax(wmx, __shfl_xor(wmx, o));
         umx = fmax(umx, __shfl_xor(umx, o));
         vmx = fmax(vmx, __shfl_xor(vmx, o));
+        fmn = fmin(fmn, __shfl_xor(fmn, o));
+        fmx = fmax(fmx, __shfl_xor(fmx, o));
     }
     const int wv = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
@@ -317,6 +339,8 @@ __global__ __launch_bounds__(256) void k_bounds(const double *__restrict__ uvw, 
         red[1][wv] = wmx;
         red[2][wv] = umx;
         red[3][wv] = vmx;
+        red[4][wv] = fmn;
+        red[5][wv] = fmx;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -325,39 +349,45 @@ __global__ __launch_bounds__(256) void k_bounds(const double *__restrict__ uvw, 
             red[1][0] = fmax(red[1][0], red[1][k]);
             red[2][0] = fmax(red[2][0], red[2][k]);
             red[3][0] = fmax(red[3][0], red[3][k]);
+            red[4][0] = fmin(red[4][0], red[4][k]);
+            red[5][0] = fmax(red[5][0], red[5][k]);
         }
-        for (int k = 0; k < 4; ++k) part[k * kBoundsBlocks + blockIdx.x] = red[k][0];
+        for (int k = 0; k < 6; ++k) part[k * kBoundsBlocks + blockIdx.x] = red[k][0];
     }
 }
 
-// out = {min su*w, max su*w, max|u|, max|v|, min freq, max freq}
+// out = {min su*w, max su*w, max|u|, max|v|, min freq, max freq, min and max
+// of the folded su*w}
 __global__ __launch_bounds__(256) void k_bounds_final(int nblocks, const double *__restrict__ part,
                                                       const double *__restrict__ freq, int nchan,
                                                       double *__restrict__ out) {
-    __shared__ double red[6][256];
-    double a[6] = {1e300, -1e300, 0.0, 0.0, 1e300, -1e300};
+    __shared__ double red[8][256];
+    double a[8] = {1e300, -1e300, 0.0, 0.0, 1e300, -1e300, 1e300, -1e300};
     for (int b = threadIdx.x; b < nblocks; b += 256) {
         a[0] = fmin(a[0], part[b]);
         a[1] = fmax(a[1], part[kBoundsBlocks + b]);
         a[2] = fmax(a[2], part[2 * kBoundsBlocks + b]);
         a[3] = fmax(a[3], part[3 * kBoundsBlocks + b]);
+        a[6] = fmin(a[6], part[4 * kBoundsBlocks + b]);
+        a[7] = fmax(a[7], part[5 * kBoundsBlocks + b]);
     }
     for (int c = threadIdx.x; c < nchan; c += 256) {
         a[4] = fmin(a[4], freq[c]);
         a[5] = fmax(a[5], freq[c]);
     }
-    for (int k = 0; k < 6; ++k) red[k][threadIdx.x] = a[k];
+    for (int k = 0; k < 8; ++k) red[k][threadIdx.x] = a[k];
     __syncthreads();
     for (int st = 128; st > 0; st >>= 1) {
         if (threadIdx.x < st) {
             const int t = threadIdx.x;
             red[0][t] = fmin(red[0][t], red[0][t + st]);
             red[4][t] = fmin(red[4][t], red[4][t + st]);
-            for (int k : {1, 2, 3, 5}) red[k][t] = fmax(red[k][t], red[k][t + st]);
+            red[6][t] = fmin(red[6][t], red[6][t + st]);
+            for (int k : {1, 2, 3, 5, 7}) red[k][t] = fmax(red[k][t], red[k][t + st]);
         }
         __syncthreads();
     }
-    if (threadIdx.x < 6) out[threadIdx.x] = red[threadIdx.x][0];
+    if (threadIdx.x < 8) out[threadIdx.x] = red[threadIdx.x][0];
 }
 
 // per-part plan metadata (one buffer, one D2H copy when the host needs it):
@@ -741,6 +771,7 @@ __device__ __forceinline__ void bucket_one(const Geo &g, int64_t v, int64_t nvis
             cr = r_;
             ci = i_;
         }
+        if (kGrid && c.conj) ci = -ci;  // (folded: after the rotation)
         if (kCompact) {
             // RecC: offsets as fractions of (1 - W/2) - offset (do_w off: w = 0)
             const double base = 1.0 - 0.5 * g.W;
@@ -924,6 +955,7 @@ __global__ __launch_bounds__(256) void k_bucket_pols(Geo g, int64_t nvis,
         RecC rc;
         rc.cre = rot ? cr * cs - ci * sn : cr;
         rc.cim = rot ? cr * sn + ci * cs : ci;
+        if (c.conj) rc.cim = -rc.cim;  // (folded: after the rotation)
         rc.lo = qu | (qv << 21);
         rc.hi = (qv >> 11) | (qw << 10);
         ps.recs[q][pos] = rc;
@@ -2711,6 +2743,7 @@ __global__ void k_bucket_f64(Geo g, int64_t nvis, const double *__restrict__ uvw
         cr = r_;
         ci = i_;
     }
+    if (kGrid && c.conj) ci = -ci;  // (folded: after the rotation)
     VisRec64 rec;
     rec.cre = cr;
     rec.cim = ci;
@@ -2994,6 +3027,7 @@ __device__ __forceinline__ void t_write(const Geo &g, const VisExtra &x, const T
             cr = r_;
             ci = i_;
         }
+        if (kGrid && p.c.conj) ci = -ci;  // (folded: after the rotation)
         Rec64 rec;
         rec.cre = cr;
         rec.cim = ci;
@@ -3018,6 +3052,7 @@ __device__ __forceinline__ void t_write(const Geo &g, const VisExtra &x, const T
             cr = r_;
             ci = i_;
         }
+        if (kGrid && p.c.conj) ci = -ci;  // (folded: after the rotation)
         if constexpr (KIND == 0) {
             const double base = 1.0 - 0.5 * g.W;
             const uint32_t qu = fix_frac(base - p.c.du, 21), qv = fix_frac(base - p.c.dv, 21);
@@ -4645,7 +4680,7 @@ static void geo_factors(Geo &g) {
 // Geometry shared by both directions: kernel, padded grid, w planes, bucket
 // granularity, row band, plane chunking.  One host sync (uvw and frequency
 // extremes) unless the bounds are given.
-static Plan plan_geometry(const Inputs &in, bool grid_mode, hipStream_t st) {
+static Plan plan_geometry_once(const Inputs &in, bool grid_mode, hipStream_t st, bool allow_fold) {
     SDP_REQUIRE(in.nx > 0 && in.ny > 0 && in.nx % 2 == 0 && in.ny % 2 == 0,
                 "npix_x and npix_y must be positive and even");
     SDP_REQUIRE(in.px > 0 && in.py > 0, "pixel sizes must be positive");
@@ -4681,6 +4716,12 @@ static Plan plan_geometry(const Inputs &in, bool grid_mode, hipStream_t st) {
 
     // uvw and frequency extremes (device) -> host, or the batch sequence's
     double *hb = pinned_host<double>(0, 6);
+    // Hermitian fold (Geo::fold): the invert of a call whose extremes the
+    // library computes itself (batches and w slabs take their bounds and plane
+    // histograms from the caller); SDP_HIP_HFOLD=0 switches it off (A/B)
+    bool fold = allow_fold && grid_mode && !in.bounds && !(in.flags & SDP_HIP_W_SLAB) &&
+                env_int("SDP_HIP_HFOLD", 1) != 0;
+    double wf_lo = 0.0, wf_hi = 0.0;  // extremes of the folded su * w (metres)
     if (in.bounds) {
         const double *b = in.bounds;
         SDP_REQUIRE(b[0] <= b[1] && b[2] >= 0 && b[3] >= 0 && b[4] > 0 && b[4] <= b[5],
@@ -4692,14 +4733,17 @@ static Plan plan_geometry(const Inputs &in, bool grid_mode, hipStream_t st) {
         hb[4] = b[4];
         hb[5] = b[5];
     } else {
-        auto *part = scratch<double>("bounds_part", 4 * kBoundsBlocks);
-        auto *bnd = scratch<double>("bounds", 6);
+        auto *part = scratch<double>("bounds_part", 6 * kBoundsBlocks);
+        auto *bnd = scratch<double>("bounds", 8);
+        hb = pinned_host<double>(0, 8);
         const int nb = (int)std::max<int64_t>(
             1, std::min<int64_t>(grid1d(in.nrow, 256), kBoundsBlocks));
         k_bounds<<<nb, 256, 0, st>>>(in.uvw, in.uvw_rs, in.nrow, g.su, part);
         k_bounds_final<<<1, 256, 0, st>>>(nb, part, in.freq, in.nchan, bnd);
-        SDP_HIP_CHECK(hipMemcpyAsync(hb, bnd, 6 * sizeof(double), hipMemcpyDeviceToHost, st));
+        SDP_HIP_CHECK(hipMemcpyAsync(hb, bnd, 8 * sizeof(double), hipMemcpyDeviceToHost, st));
         SDP_HIP_CHECK(hipStreamSynchronize(st));
+        wf_lo = hb[6];
+        wf_hi = hb[7];
     }
     const double fmin_ = hb[4], fmax_ = hb[5];
     SDP_REQUIRE(fmin_ > 0, "frequencies must be positive");
@@ -4738,12 +4782,33 @@ static Plan plan_geometry(const Inputs &in, bool grid_mode, hipStream_t st) {
         g.nps = hi - lo;
         g.nplanes = g.nps + g.W - 1;
     }
+    // The fold never changes the plane layout: w0, dw, nplanes and nps above
+    // come from the unfolded w range (a batched call of the same data gets the
+    // same layout, and the row-by-w partition relies on small-|w| intervals
+    // having few planes).  So the fold is on only when the folded w extremes,
+    // scaled by the frequency range as wmin / wmax are, have their first plane
+    // (vis_coord_v's expression) in [0, nps) of that layout, with a margin of
+    // 1e-6 plane for the rounding of w * s per channel; else the plan runs
+    // unfolded.  Without w-stacking there is nothing to check.
+    if (fold && g.do_w && any) {
+        const double flo = std::min(wf_lo * slo, wf_lo * shi);
+        const double fhi = std::max(wf_hi * slo, wf_hi * shi);
+        const double idw = 1.0 / g.dw, margin = 1.0e-6;
+        const double plo = std::fma(flo, idw, -g.kpw0) - 0.5 * g.W;
+        const double phi = std::fma(fhi, idw, -g.kpw0) - 0.5 * g.W;
+        // first plane floor(p) + 1 in [0, nps)  <=>  -1 <= p < nps - 1
+        fold = std::isfinite(plo) && std::isfinite(phi) && plo >= -1.0 + margin &&
+               phi < (double)(g.nps - 1) - margin;
+    }
+    g.fold = fold ? 1 : 0;
     // bucket window (origins only: the footprints' halo may leave it): the
     // `al`-aligned cell range [ng/2 - reach, ng/2 + reach), or the whole
-    // (al-rounded) axis when that reaches an edge
-    auto window = [&](double m, int ng, int al, int &w0, int &wn) {
+    // (al-rounded) axis when that reaches an edge.  `half` (the x window of a
+    // folded plan): every origin has a >= 0, so the range starts at
+    // ng/2 - ceil(W/2) - 2
+    auto window = [&](double m, int ng, int al, int &w0, int &wn, bool half = false) {
         const int reach = (int)std::ceil(m + 0.5 * g.W) + 2;
-        int lo = (ng / 2 - reach) & ~(al - 1);
+        int lo = (ng / 2 - (half ? (g.W + 1) / 2 + 2 : reach)) & ~(al - 1);
         int hi = ((ng / 2 + reach + al - 1) / al) * al;
         if (lo <= 0 || hi >= ng) {
             lo = 0;
@@ -4771,7 +4836,7 @@ static Plan plan_geometry(const Inputs &in, bool grid_mode, hipStream_t st) {
         (!(in.flags & SDP_HIP_KEEP_BUCKETS) || b2 == 2) &&
         env_int("SDP_HIP_BUCKET", 0) != kTileCoarse) {
         int x0, nx_, y0, ny_;
-        window(amax, g.ngx, kTile, x0, nx_);
+        window(amax, g.ngx, kTile, x0, nx_, g.fold != 0);
         window(bmax, g.ngy, kTile, y0, ny_);
         const int64_t nbins = (int64_t)(nx_ / kTile) * (ny_ / kTile) * g.nps;
         // the padded record total and the cell bases are 32-bit: every
@@ -4796,7 +4861,7 @@ static Plan plan_geometry(const Inputs &in, bool grid_mode, hipStream_t st) {
         // x (rows) only: the y stride stays ngy, since a compacted y range
         // packs the hot histogram counters of the uv core closer together and
         // measured 2x slower count-pass atomics on C2
-        window(amax, g.ngx, kGridAlign, g.wx0, g.wnx);
+        window(amax, g.ngx, kGridAlign, g.wx0, g.wnx, g.fold != 0);
         g.wy0 = 0;
         g.wny = g.ngy;
     }
@@ -4846,11 +4911,12 @@ static Plan plan_geometry(const Inputs &in, bool grid_mode, hipStream_t st) {
     }
     SDP_REQUIRE((double)g.ntiles * g.nps * g.salt < 4.0e9, "too many (plane, tile) buckets");
 
-    // grid rows reached by any footprint (centred storage)
+    // grid rows reached by any footprint (centred storage); a folded plan's
+    // footprints start at ngx / 2 - ceil(W / 2) + 1 or above
     {
         const double amax = umax * in.px * g.ngx;
         const int reach = (int)std::ceil(amax) + g.W + 1;
-        P.row_lo = std::max(0, g.ngx / 2 - reach);
+        P.row_lo = std::max(0, g.ngx / 2 - (g.fold ? g.W + 1 : reach));
         P.row_hi = std::min(g.ngx, g.ngx / 2 + reach);
         if (2 * reach >= g.ngx) {
             P.row_lo = 0;
@@ -4945,6 +5011,19 @@ static Plan plan_geometry(const Inputs &in, bool grid_mode, hipStream_t st) {
              : P.subpad ? scratch<VisRec>("recs", (std::max<int64_t>(nvis, 1) + 1) / 2 + 1)  // RecC
                         : scratch<VisRec>("recs", std::max<int64_t>(nvis, 1));
     if (P.subpad) P.cls = scratch<uint8_t>("rec_cls", std::max<int64_t>(nvis, 1));
+    return P;
+}
+
+// A folded plan whose planes do not all stay resident is planned again
+// unfolded: the plane-chunked invert is the fall-back of a batch sequence
+// that cannot hold its planes (the streamed host invert), and it computes
+// what the (unfolded) batches would have -- at epsilon 1e-12 the fold moves
+// the result by the NUFFT's own approximation error (~2e-12: the mirrored w
+// sits at another offset between the planes).  Re-gridding every record once
+// per plane chunk dominates such a call anyway.
+static Plan plan_geometry(const Inputs &in, bool grid_mode, hipStream_t st) {
+    Plan P = plan_geometry_once(in, grid_mode, st, true);
+    if (P.g.fold && P.chunk_planes < P.g.nplanes) P = plan_geometry_once(in, grid_mode, st, false);
     return P;
 }
 
@@ -5483,6 +5562,7 @@ static void fill_info(const Plan &P, sdp_hip_wgrid_info *info) {
     info->fp64 = P.f64 ? 1 : 0;
     info->tiled = P.g.tiled;
     info->grid_launches = (P.g.nplanes + P.chunk_planes - 1) / P.chunk_planes;
+    info->folded = P.g.fold;
 }
 
 // Pruned 2-D FFT of each resident plane.  The uv grid is non-zero only in

@@ -65,6 +65,7 @@ class WGridInfo(ctypes.Structure):
         ("padded", c_int),
         ("fp64", c_int),
         ("tiled", c_int),
+        ("folded", c_int),
     ]
 
     def as_dict(self):
