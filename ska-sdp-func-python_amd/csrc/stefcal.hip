@@ -244,7 +244,8 @@ __global__ __launch_bounds__(kThreads) void k_iter(Dims d, const float2 *__restr
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // uniform: SGPR block math
     constexpr int K = kRowsInFlight;
     static_assert(K == 8, "the reduce-scatter below sums 8 rows");
-    const bool b5 = lane & 32, b4 = lane & 16, b3 = lane & 8;
+    [[maybe_unused]] const bool b5 = lane & 32, b4 = lane & 16;  // (the __shfl_xor variant)
+    const bool b3 = lane & 8;
     const int nblk = (na + 63) / 64;
     for (int k = 0; k * kWaves < nblk; ++k) {
         const int c = (k & 1) ? (k + 1) * kWaves - 1 - wave : k * kWaves + wave;

@@ -42,6 +42,7 @@
 #include <vector>
 
 #include "sdp_common.h"
+#include "wstack_fx_fft.h"
 
 namespace sdp {
 namespace wstack {
@@ -153,11 +154,6 @@ struct FineItem {
 static int env_int(const char *name, int dflt) {
     const char *e = std::getenv(name);
     return e ? std::atoi(e) : dflt;
-}
-
-__device__ __forceinline__ unsigned long long ord_enc(double d) {
-    long long i = __double_as_longlong(d);
-    return i < 0 ? ~(unsigned long long)i : ((unsigned long long)i | 0x8000000000000000ull);
 }
 
 // ES kernel exp(beta (sqrt(1 - x^2) - 1)), x = 2t/W; `beta_l2e` = beta*log2(e)
@@ -532,6 +528,17 @@ template <class T>
 struct TypeTag {
     using type = T;
 };
+
+// Runtime value -> template argument: calls f(std::integral_constant<int, k>{})
+// with k = v for v in [Lo, Hi) and k = Hi for every other v, so f's body is
+// instantiated for exactly Lo .. Hi.
+template <int Lo, int Hi, class F>
+inline void dispatch_int(int v, F &&f) {
+    if constexpr (Lo < Hi) {
+        if (v != Lo) return dispatch_int<Lo + 1, Hi>(v, f);
+    }
+    f(std::integral_constant<int, Lo>{});
+}
 
 template <class VT>
 __device__ __forceinline__ double2 eff_vis_d(const VT *vis, int64_t vrs, int64_t vcs,
@@ -1378,7 +1385,6 @@ __device__ __forceinline__ Item load_fine_item(const FineItem *items, uint32_t w
     return it;
 }
 
-
 // MFMA kernels' operand types and wave-level helpers
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
@@ -1570,10 +1576,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4))) void
     static_assert(NG == 1 || NG == 2 || NG == 4 || NG == 8 || NG == 16, "units of 1-16 groups");
     // (NG = 2, 8, 16 are valid but measured slower on C4; only 1 and 4 are launched)
     extern __shared__ __attribute__((aligned(16))) float2 tile[];
-    constexpr int NQ = WS ? W : 1;
     constexpr int kRegX = PadUnit<NG>::RGX, kRegY = PadUnit<NG>::RGY;
-    // cells a footprint of the unit reaches
-    constexpr int RX = PadUnit<NG>::TX + W - 1, RY = PadUnit<NG>::TY + W - 1;
     float *const reg = reinterpret_cast<float *>(tile);  // [kRegX][kRegY][16]
     float4 *const stage = reinterpret_cast<float4 *>(reg + kRegX * kRegY * kRegCell);
     float *const blk = reinterpret_cast<float *>(stage + kTapBatch);  // [kTapBatch][kTapRec]
@@ -2195,197 +2198,6 @@ __global__ void k_screen_adj_t(Geo g, const double *__restrict__ dirty, int64_t 
     } else {
         dst[0] = cplx<T>(val, 0.0);
     }
-}
-
-// ---- fused x-FFT + w screens (fp32 planes, power-of-two ngx) ------------
-// One workgroup per image row iy.  Per plane of the batch the T row (c64,
-// N = ngx points) is transformed in LDS by a Stockham mixed-radix FFT: N / 16
-// threads hold 16 points each, radix-16 passes and at most one radix-2/4/8
-// pass (natural-order output, no bit reversal), LDS padded by one element
-// per 16 so the strided pass-0 writes are conflict-free.  The twiddles do not
-// depend on the plane: each thread's w, w^2, w^4, w^8 per pass are computed
-// once by sincospif (exact fractions) and the other powers by at most three
-// products.  The invert screens the FFT's image columns straight from LDS
-// into fp64 registers (the x-spectra are never written), the predict
-// screens the image into the FFT's input in LDS (the zero-filled x-FFT input
-// is never written or read).
-__device__ __forceinline__ float2 cmulf(float2 a, float2 b) {
-    return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-
-// e^{SG 2 pi i m / 16} (SG = +1: backward, -1: forward), m a constant
-template <int SG>
-__device__ __forceinline__ float2 root16(int m) {
-    constexpr float c16[16] = {1.0f,
-                               0.92387953251128673848f,
-                               0.70710678118654752440f,
-                               0.38268343236508978178f,
-                               0.0f,
-                               -0.38268343236508978178f,
-                               -0.70710678118654752440f,
-                               -0.92387953251128673848f,
-                               -1.0f,
-                               -0.92387953251128673848f,
-                               -0.70710678118654752440f,
-                               -0.38268343236508978178f,
-                               0.0f,
-                               0.38268343236508978178f,
-                               0.70710678118654752440f,
-                               0.92387953251128673848f};
-    m &= 15;
-    return make_float2(c16[m], SG * c16[(m + 12) & 15]);  // sin = cos(. - pi/2)
-}
-
-// R-point DFT (R = 2, 4, 8, 16) of v[0..R) in registers, radix-2
-// decimation in frequency: the result leaves bit-reversed (out[bitrev(r)] =
-// v[r]); the callers index it through fx_brev
-template <int R, int SG>
-__device__ __forceinline__ void fx_dft(float2 *v) {
-#pragma unroll
-    for (int L = R; L >= 2; L >>= 1) {
-        const int h = L >> 1;
-#pragma unroll
-        for (int s = 0; s < R; s += L) {
-#pragma unroll
-            for (int k = 0; k < h; ++k) {
-                const float2 a = v[s + k], b = v[s + k + h];
-                v[s + k] = make_float2(a.x + b.x, a.y + b.y);
-                const float2 d = make_float2(a.x - b.x, a.y - b.y);
-                v[s + k + h] = k == 0 ? d : cmulf(d, root16<SG>(k * (16 / L)));
-            }
-        }
-    }
-}
-
-template <int R>
-__device__ __forceinline__ constexpr int fx_brev(int r) {
-    int o = 0;
-    for (int b = 1, t = R >> 1; b < R; b <<= 1, t >>= 1)
-        if (r & b) o |= t;
-    return o;
-}
-
-__device__ __forceinline__ int fx_pad(int i) { return i + (i >> 4); }
-// fx_pad(t + c), pt = fx_pad(t), c a multiple of T: for T % 16 == 0 it is
-// pt + 17 c / 16 (an immediate offset from one base)
-template <int T>
-__device__ __forceinline__ int fx_padc(int t, int pt, int c) {
-    if constexpr (T % 16 == 0) return pt + (c / 16) * 17;
-    else return fx_pad(t + c);
-}
-
-// the 15 twiddles w^r, r = 1..15, from w, w^2, w^4, w^8
-__device__ __forceinline__ void fx_powers(const float2 (&b)[4], float2 *w) {
-    w[1] = b[0];
-    w[2] = b[1];
-    w[3] = cmulf(b[1], b[0]);
-    w[4] = b[2];
-    w[5] = cmulf(b[2], b[0]);
-    w[6] = cmulf(b[2], b[1]);
-    w[7] = cmulf(b[2], w[3]);
-#pragma unroll
-    for (int r = 1; r < 8; ++r) w[8 + r] = cmulf(b[3], w[r]);
-    w[8] = b[3];
-}
-
-template <int LOGN>
-struct FxShape {
-    static constexpr int N = 1 << LOGN;
-    static constexpr int T = N / 16;          // threads
-    static constexpr int P16 = LOGN / 4;      // radix-16 passes
-    static constexpr int RR = 1 << (LOGN % 4);  // last pass radix (1: none)
-    static constexpr int LDS = N + N / 16;    // padded float2 elements
-    // twiddle table (fx_twiddles), copied into LDS behind the data by each
-    // workgroup: radix-16 pass p >= 1 at tw_off(p), w and w^4 per k < 16^p;
-    // the last pass's e^{2 pi i t / N} at tw_off(P16)
-    static constexpr int tw_off(int p) { return p <= 1 ? 0 : tw_off(p - 1) + 2 * (1 << (4 * (p - 1))); }
-    static constexpr int TW = tw_off(P16) + T;
-    static constexpr size_t lds_bytes() { return (size_t)(LDS + TW) * 8; }
-};
-
-// the transform of the row held as v[r] = X[t + r T] (pass 0's inputs) into
-// buf (natural order, padded); ends with the workgroup synchronised
-template <int LOGN, int SG>
-__device__ __forceinline__ void fx_fft(float2 (&v)[16], float2 *buf, const float2 *__restrict__ twt,
-                                       int t) {
-    using S = FxShape<LOGN>;
-    // pass 0 (Ns = 1): no twiddles, outputs to 16 t + r
-    fx_dft<16, SG>(v);
-    {
-        float2 *const o = buf + 17 * t;  // fx_pad(16 t + r) = 17 t + r
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[r] = v[fx_brev<16>(r)];
-    }
-    __syncthreads();
-    const int pt = fx_pad(t);
-    int ns = 16;
-#pragma unroll
-    for (int p = 1; p < S::P16; ++p) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) v[r] = buf[fx_padc<S::T>(t, pt, r * S::T)];
-        __syncthreads();
-        // twiddles w^r, w = e^{SG 2 pi i k / (16 Ns)}, k = t mod Ns
-        const int k = t % ns, d = (t / ns) * ns * 16 + k;
-        {
-            // (kk opaque: the twiddles are loaded and multiplied out per
-            // transform, not hoisted out of the caller's plane loop, where
-            // they held ~60 VGPRs)
-            int kk = k;
-            asm volatile("" : "+v"(kk));
-            float2 b[4], w[16];
-            const float4 q0 = *reinterpret_cast<const float4 *>(twt + S::tw_off(p) + 2 * kk);
-            b[0] = make_float2(q0.x, SG * q0.y);
-            b[2] = make_float2(q0.z, SG * q0.w);
-            b[1] = cmulf(b[0], b[0]);
-            b[3] = cmulf(b[2], b[2]);
-            fx_powers(b, w);
-#pragma unroll
-            for (int r = 1; r < 16; ++r) v[r] = cmulf(v[r], w[r]);
-        }
-        fx_dft<16, SG>(v);
-        const int pd = fx_pad(d);  // (ns >= 16: r ns is a multiple of 16)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) buf[pd + r * ns + ((r * ns) >> 4)] = v[fx_brev<16>(r)];
-        __syncthreads();
-        ns *= 16;
-    }
-    if constexpr (S::RR > 1) {
-        // last pass, Ns = N / RR: butterfly j = t + T m reads and writes
-        // X[j + r N / RR] in place (no hazard across threads)
-        constexpr int RR = S::RR, NB = 16 / RR, STR = S::N / RR;
-        int tt = t;
-        asm volatile("" : "+v"(tt));
-        const float2 l0 = twt[S::tw_off(S::P16) + tt], last = make_float2(l0.x, SG * l0.y);
-#pragma unroll
-        for (int m = 0; m < NB; ++m) {
-            float2 u[RR];
-            const int j = t + S::T * m;
-#pragma unroll
-            for (int r = 0; r < RR; ++r) u[r] = buf[fx_padc<S::T>(t, pt, S::T * m + r * STR)];
-            // twiddle w_j^r, w_j = e^{SG 2 pi i j / N} = last * e^{SG 2 pi i m / 16}
-            const float2 wj = m == 0 ? last : cmulf(last, root16<SG>(m));
-            float2 wr = wj;
-#pragma unroll
-            for (int r = 1; r < RR; ++r) {
-                u[r] = cmulf(u[r], wr);
-                if (r + 1 < RR) wr = cmulf(wr, wj);
-            }
-            fx_dft<RR, SG>(u);
-#pragma unroll
-            for (int r = 0; r < RR; ++r) buf[fx_padc<S::T>(t, pt, S::T * m + r * STR)] = u[fx_brev<RR>(r)];
-        }
-        __syncthreads();
-    }
-}
-
-// the workgroup's LDS copy of the twiddle table (behind the data buffer)
-template <int LOGN>
-__device__ __forceinline__ float2 *fx_twl(float2 *fbuf, const float2 *__restrict__ twg, int t) {
-    using S = FxShape<LOGN>;
-    float2 *const twl = fbuf + S::LDS;
-    for (int i = t; i < S::TW; i += S::T) twl[i] = twg[i];
-    __syncthreads();
-    return twl;
 }
 
 // pass 0's inputs v[r] = X[t + r T] of one T row; the columns outside the
@@ -4084,7 +3896,7 @@ __global__ __launch_bounds__(64 * kDeg64Waves) void k_degrid_f64_mfma(
             kb < nblk ? stage64_load(recs, btab[kb], (int)(bcel[kb] >> 8), lane) : Stage64{};
         for (; kb < nblk; kb += kDeg64Waves) {
             {
-                const uint32_t b0 = btab[kb], cn = bcel[kb];
+                const uint32_t cn = bcel[kb];
                 const int c = (int)(cn & 15u);
                 const int nb = (int)(cn >> 8);
                 const Stage64 cur_s = nxt;
@@ -4264,14 +4076,6 @@ static hipfftHandle fft_plan_1d(int n, int stride, int dist, int batch, hipStrea
     return h;
 }
 
-static double ord_dec(unsigned long long u) {
-    const long long i = (u & 0x8000000000000000ull) ? (long long)(u & 0x7fffffffffffffffull)
-                                                    : (long long)~u;
-    double d;
-    std::memcpy(&d, &i, sizeof(d));
-    return d;
-}
-
 static int kernel_support(double epsilon) {
     const double eps = std::max(epsilon, 1.0e-7);
     const int W = (int)std::ceil(-std::log10(eps / 10.0) - 1e-9);
@@ -4283,7 +4087,6 @@ static int kernel_support64(double epsilon) {
     const int W = (int)std::ceil(-std::log10(std::max(epsilon, 1e-15) / 10.0) - 1e-9);
     return std::min(std::max(W, kMinW64), kMaxW64);
 }
-
 
 // Pinned host staging for the plan's small device->host reads (pageable
 // destinations go through a slow staging copy).  Byte offset `off` into a
@@ -5038,20 +4841,13 @@ struct TypedIn {
     int wt, fb;
     template <class F>
     void dispatch(F launch) const {
-        using I0 = std::integral_constant<int, 0>;
-        using I1 = std::integral_constant<int, 1>;
-        using I4 = std::integral_constant<int, 4>;
-        using I8 = std::integral_constant<int, 8>;
-        if (fb == 0) {
-            if (wt == 4) launch(I4{}, I0{});
-            else launch(I8{}, I0{});
-        } else if (fb == 1) {
-            if (wt == 4) launch(I4{}, I1{});
-            else launch(I8{}, I1{});
-        } else {
-            if (wt == 4) launch(I4{}, I8{});
-            else launch(I8{}, I8{});
-        }
+        dispatch_int<0, 1>(wt == 4 ? 0 : 1, [&](auto w) {
+            using WT = std::integral_constant<int, decltype(w)::value ? 8 : 4>;
+            dispatch_int<0, 2>(fb == 0 ? 0 : fb == 1 ? 1 : 2, [&](auto f) {
+                constexpr int k = decltype(f)::value;
+                launch(WT{}, std::integral_constant<int, k == 2 ? 8 : k>{});
+            });
+        });
     }
 };
 
@@ -5241,16 +5037,11 @@ static void bucket_part(Plan &P, const Inputs &in, bool grid_mode, hipStream_t s
                 ti.dispatch([&](auto wt_tag, auto fb_tag) {
                     constexpr int WT = decltype(wt_tag)::value, FB = decltype(fb_tag)::value;
                     const VT *vp = static_cast<const VT *>(in.vis);
-#define SDP_POLS(N)                                                                         \
-    k_bucket_pols<VT, WT, FB, N><<<nb, 256, 0, st>>>(g, pt.nvis, in.uvw, in.uvw_rs, fsc, vp, \
-                                                     in.vrs, in.vcs, ti.x, *pols, pt.offs, kr)
-                    switch (pols->npo) {
-                        case 1: SDP_POLS(1); break;
-                        case 2: SDP_POLS(2); break;
-                        case 3: SDP_POLS(3); break;
-                        default: SDP_POLS(4); break;
-                    }
-#undef SDP_POLS
+                    dispatch_int<1, 4>(pols->npo, [&](auto n) {
+                        k_bucket_pols<VT, WT, FB, decltype(n)::value><<<nb, 256, 0, st>>>(
+                            g, pt.nvis, in.uvw, in.uvw_rs, fsc, vp, in.vrs, in.vcs, ti.x, *pols,
+                            pt.offs, kr);
+                    });
                 });
             };
             if (in.vis_dtype == SDP_HIP_C128) go(TypeTag<double2>{});
@@ -5351,18 +5142,6 @@ static void launch_grid_f64(const Plan &P, int p_lo, int p_hi, hipStream_t st) {
         reinterpret_cast<double *>(P.grid), p_lo, p_hi);
 }
 
-#define SDP_W64_DISPATCH(W, CALL) \
-    switch (W) {                  \
-        case 9: CALL(9); break;   \
-        case 10: CALL(10); break; \
-        case 11: CALL(11); break; \
-        case 12: CALL(12); break; \
-        case 13: CALL(13); break; \
-        case 14: CALL(14); break; \
-        case 15: CALL(15); break; \
-        default: CALL(16); break; \
-    }
-
 // The fp64 kernels' tap polynomials (es_taps_poly) for support W and shape
 // beta: per tap j, the interpolant of exp(beta (sqrt(1 - x^2) - 1)), x =
 // (s - W/2 + j) 2 / W, at the kPoly64 + 1 Chebyshev nodes of s in [0, 1],
@@ -5394,7 +5173,7 @@ static const double *es_poly64_table(int W, double beta, hipStream_t st) {
             cheb[d] = a * (d == 0 ? 1.0L : 2.0L) / N;
         }
         // Chebyshev -> monomial: T_0 = 1, T_1 = t, T_{n+1} = 2 t T_n - T_{n-1}
-        long double mono[N] = {}, tm1[N] = {}, t0[N] = {}, t1[N] = {};
+        long double mono[N] = {}, t0[N] = {}, t1[N] = {};
         t0[0] = 1;
         t1[1] = 1;
         for (int d = 0; d < N; ++d) {
@@ -5410,7 +5189,6 @@ static const double *es_poly64_table(int W, double beta, hipStream_t st) {
                 }
             }
         }
-        (void)tm1;
         for (int d = 0; d < N; ++d) tab[(size_t)d * kPolyStride + j] = (double)mono[d];
     }
     double *dptr = nullptr;
@@ -5467,34 +5245,33 @@ static void launch_degrid_f64_mfma(const Plan &P, int p_lo, int p_hi, VT *vis, i
 }
 
 static void grid_f64(const Plan &P, int p_lo, int p_hi, hipStream_t st) {
-#define SDP_G64(WW)                                                                    \
-    (P.pad64 ? (P.g.do_w ? launch_grid_f64_mfma<WW, true>(P, p_lo, p_hi, st)          \
-                         : launch_grid_f64_mfma<WW, false>(P, p_lo, p_hi, st))        \
-             : (P.g.do_w ? launch_grid_f64<WW, true>(P, p_lo, p_hi, st)               \
-                         : launch_grid_f64<WW, false>(P, p_lo, p_hi, st)))
-    SDP_W64_DISPATCH(P.g.W, SDP_G64);
-#undef SDP_G64
+    dispatch_int<kMinW64, kMaxW64>(P.g.W, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        if (P.pad64) {
+            if (P.g.do_w) launch_grid_f64_mfma<W, true>(P, p_lo, p_hi, st);
+            else launch_grid_f64_mfma<W, false>(P, p_lo, p_hi, st);
+        } else {
+            if (P.g.do_w) launch_grid_f64<W, true>(P, p_lo, p_hi, st);
+            else launch_grid_f64<W, false>(P, p_lo, p_hi, st);
+        }
+    });
 }
 
-template <class VT>
-static void degrid_f64(const Plan &P, int p_lo, int p_hi, VT *vis, int64_t vrs, int64_t vcs,
-                       int accumulate, const OutConv &oc, hipStream_t st) {
+static void degrid_f64(const Plan &P, int p_lo, int p_hi, void *vis, int vis_dtype, int64_t vrs,
+                int64_t vcs, int accumulate, const OutConv &oc, hipStream_t st) {
     SDP_REQUIRE(P.mfma64, "the fp64 predict needs one-cell buckets");
-#define SDP_D64(WW)                                                                             \
-    (P.g.do_w ? launch_degrid_f64_mfma<WW, true, VT>(P, p_lo, p_hi, vis, vrs, vcs, accumulate, oc, \
-                                                     st)                                        \
-              : launch_degrid_f64_mfma<WW, false, VT>(P, p_lo, p_hi, vis, vrs, vcs, accumulate, \
-                                                      oc, st))
-    SDP_W64_DISPATCH(P.g.W, SDP_D64);
-#undef SDP_D64
-}
-
-template <int W>
-static void launch_grid(const Plan &P, int p_lo, int p_hi, hipStream_t st) {
-    // (fp32 inverts are always 4-padded: one-cell plans by the bucketing,
-    // large grids by the sub-sort)
-    if (P.g.do_w) return launch_grid_mfma_pad<W, true>(P, p_lo, p_hi, st);
-    return launch_grid_mfma_pad<W, false>(P, p_lo, p_hi, st);
+    dispatch_int<kMinW64, kMaxW64>(P.g.W, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        auto go = [&](auto *v) {
+            using VT = std::remove_pointer_t<decltype(v)>;
+            if (P.g.do_w)
+                launch_degrid_f64_mfma<W, true, VT>(P, p_lo, p_hi, v, vrs, vcs, accumulate, oc, st);
+            else
+                launch_degrid_f64_mfma<W, false, VT>(P, p_lo, p_hi, v, vrs, vcs, accumulate, oc, st);
+        };
+        if (vis_dtype == SDP_HIP_C128) go(static_cast<double2 *>(vis));
+        else go(static_cast<float2 *>(vis));
+    });
 }
 
 // the degridder's store sink (kDegridSinkBlocks x 64 float2 per device,
@@ -5528,22 +5305,23 @@ static void launch_degrid_mfma(const Plan &P, int p_lo, int p_hi, float2 *acc, h
             P.g, P.recs, n, P.pt.fitems + per * (size_t)r.first, P.grid, p_lo, p_hi, acc, sink);
 }
 
-template <int W>
-static void launch_degrid(const Plan &P, int p_lo, int p_hi, float2 *acc, hipStream_t st) {
-    if (P.g.do_w) return launch_degrid_mfma<W, true>(P, p_lo, p_hi, acc, st);
-    return launch_degrid_mfma<W, false>(P, p_lo, p_hi, acc, st);
+// (fp32 inverts are always 4-padded: one-cell plans by the bucketing, large
+// grids by the sub-sort)
+static void grid_f32(const Plan &P, int p_lo, int p_hi, hipStream_t st) {
+    dispatch_int<2, kMaxW>(P.g.W, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        if (P.g.do_w) launch_grid_mfma_pad<W, true>(P, p_lo, p_hi, st);
+        else launch_grid_mfma_pad<W, false>(P, p_lo, p_hi, st);
+    });
 }
 
-#define SDP_W_DISPATCH(W, CALL) \
-    switch (W) {                \
-        case 2: CALL(2); break; \
-        case 3: CALL(3); break; \
-        case 4: CALL(4); break; \
-        case 5: CALL(5); break; \
-        case 6: CALL(6); break; \
-        case 7: CALL(7); break; \
-        default: CALL(8); break; \
-    }
+static void degrid_f32(const Plan &P, int p_lo, int p_hi, float2 *acc, hipStream_t st) {
+    dispatch_int<2, kMaxW>(P.g.W, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        if (P.g.do_w) launch_degrid_mfma<W, true>(P, p_lo, p_hi, acc, st);
+        else launch_degrid_mfma<W, false>(P, p_lo, p_hi, acc, st);
+    });
+}
 
 static void fill_info(const Plan &P, sdp_hip_wgrid_info *info) {
     if (!info) return;
@@ -5794,12 +5572,13 @@ static void launch_xfft_screen_fwd(const Plan &P, int p_begin, int nb, double *d
 static void xfft_screen_fwd(const Plan &P, int p_begin, int nb, double *dirty, int64_t sx,
                             int64_t sy, int accumulate, const double *tab, hipStream_t st,
                             StageTimer &t2) {
-    switch (xfft_log2(P)) {
-#define SDP_FX(L) \
-    case L: t2.mark(); launch_xfft_screen_fwd<L>(P, p_begin, nb, dirty, sx, sy, accumulate, tab, st); break;
-    SDP_FX(7) SDP_FX(8) SDP_FX(9) SDP_FX(10) SDP_FX(11) SDP_FX(12) SDP_FX(13) SDP_FX(14)
-#undef SDP_FX
-    default:
+    if (const int l = xfft_log2(P)) {
+        t2.mark();
+        dispatch_int<7, 14>(l, [&](auto L) {
+            launch_xfft_screen_fwd<decltype(L)::value>(P, p_begin, nb, dirty, sx, sy, accumulate,
+                                                       tab, st);
+        });
+    } else {
         fft_rows_x(P, nb, HIPFFT_BACKWARD, st, P.spec_in);
         t2.mark();
         screen_fwd(P, p_begin, nb, dirty, sx, sy, accumulate, tab, st);
@@ -5830,12 +5609,12 @@ static void launch_screen_adj_xfft(const Plan &P, const double *dirty, int64_t s
 static void screen_adj_xfft(const Plan &P, const double *dirty, int64_t sx, int64_t sy,
                             int p_begin, int nb, const double *tab, hipStream_t st,
                             StageTimer &t2) {
-    switch (xfft_log2(P)) {
-#define SDP_FX(L) \
-    case L: launch_screen_adj_xfft<L>(P, dirty, sx, sy, p_begin, nb, tab, st); t2.mark(); break;
-    SDP_FX(7) SDP_FX(8) SDP_FX(9) SDP_FX(10) SDP_FX(11) SDP_FX(12) SDP_FX(13) SDP_FX(14)
-#undef SDP_FX
-    default:
+    if (const int l = xfft_log2(P)) {
+        dispatch_int<7, 14>(l, [&](auto L) {
+            launch_screen_adj_xfft<decltype(L)::value>(P, dirty, sx, sy, p_begin, nb, tab, st);
+        });
+        t2.mark();
+    } else {
         screen_adj(P, dirty, sx, sy, p_begin, nb, tab, st);
         t2.mark();
         fft_rows_x(P, nb, HIPFFT_FORWARD, st, P.spec_adj);
@@ -6083,6 +5862,52 @@ static void subsort_items(Plan &P, hipStream_t st) {
     SDP_HIP_CHECK(hipGetLastError());
 }
 
+// *out += the sum of a pass's weight-sum slots
+static void sum_slots(const double *slots, double *out, hipStream_t st) {
+    k_sum_slots<<<1, 64, 0, st>>>(slots, out);
+}
+
+// the npv output pols of every visibility = 0 (a predict that does not accumulate)
+static void zero_vis(const Inputs &in, void *vis, const OutConv &oc, hipStream_t st) {
+    const int64_t nvis = in.nrow * (int64_t)in.nchan;
+    if (nvis <= 0) return;
+    if (in.vis_dtype == SDP_HIP_C128)
+        k_zero_vis<double2><<<grid1d(nvis, 256), 256, 0, st>>>(in.nrow, in.nchan, (double2 *)vis,
+                                                                in.vrs, in.vcs, oc);
+    else
+        k_zero_vis<float2><<<grid1d(nvis, 256), 256, 0, st>>>(in.nrow, in.nchan, (float2 *)vis,
+                                                               in.vrs, in.vcs, oc);
+    SDP_HIP_CHECK(hipGetLastError());
+}
+
+// the fp32 predict's write-back: the records' degridded sums accs[q] of the
+// npo image pols through their conversions oc[q] into the visibilities
+static void finalize_vis(const Plan &P, const Inputs &in, int npo, float2 *const *accs,
+                  const OutConv *oc, void *vis, int accumulate, hipStream_t st) {
+    if (P.pt.nvis <= 0) return;
+    const unsigned nb = std::min<unsigned>(grid1d(P.pt.nvis, 256), 16384);
+    auto go = [&](auto *v) {
+        using VT = std::remove_pointer_t<decltype(v)>;
+        if (npo == 1) {
+            k_finalize<VT><<<nb, 256, 0, st>>>(P.pt.nrec, in.nchan, P.recs, accs[0], v, in.vrs,
+                                               in.vcs, accumulate, oc[0]);
+            return;
+        }
+        PolAccs pa;
+        for (int q = 0; q < npo; ++q) {
+            pa.a[q] = accs[q];
+            pa.oc[q] = oc[q];
+        }
+        dispatch_int<2, 4>(npo, [&](auto n) {
+            k_finalize_pols<VT, decltype(n)::value><<<nb, 256, 0, st>>>(
+                P.pt.nrec, in.nchan, P.recs, pa, v, in.vrs, in.vcs, accumulate);
+        });
+    };
+    if (in.vis_dtype == SDP_HIP_C128) go(static_cast<double2 *>(vis));
+    else go(static_cast<float2 *>(vis));
+    SDP_HIP_CHECK(hipGetLastError());
+}
+
 // Record `e` on `from` and make `to` wait for it.
 static void stream_after(hipStream_t to, hipStream_t from) {
     hipEvent_t e;
@@ -6110,6 +5935,103 @@ struct SlotGuard {
     }
     ~SlotGuard() { ws_slot() = 0; }
 };
+
+// Work queued on the slot's auxiliary stream behind what the call's stream
+// `st` holds so far; `st` waits for it once (join: at the first plane pass, or
+// when the call ends without one).
+struct AuxWork {
+    hipStream_t st;
+    hipEvent_t done = nullptr;
+    explicit AuxWork(hipStream_t s) : st(s) {}
+    AuxWork(const AuxWork &) = delete;
+    AuxWork &operator=(const AuxWork &) = delete;
+    template <class F>
+    void start(F work) {
+        hipStream_t aux = aux_stream();
+        stream_after(aux, st);
+        work(aux);
+        SDP_HIP_CHECK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+        SDP_HIP_CHECK(hipEventRecord(done, aux));
+    }
+    // false: nothing outstanding
+    bool join() {
+        if (!done) return false;
+        SDP_HIP_CHECK(hipStreamWaitEvent(st, done, 0));
+        hipEvent_t e = done;
+        done = nullptr;
+        SDP_HIP_CHECK(hipEventDestroy(e));
+        return true;
+    }
+    ~AuxWork() {
+        if (!done) return;  // (an error left the call early)
+        (void)hipStreamWaitEvent(st, done, 0);
+        (void)hipEventDestroy(done);
+    }
+};
+
+struct StageMs {
+    float grid = 0, fft = 0, screen = 0;
+};
+
+// the end of a call: the plan's facts and the stage times into *info
+static void finish_info(const Plan &P, StageTimer &tm, const StageMs &ms,
+                        sdp_hip_wgrid_info *info) {
+    tm.mark();
+    fill_info(P, info);
+    if (!info) return;
+    // prep: everything on the call's stream that is not gridding, FFT or
+    // screen -- geometry, bucketing, band zeroing not hidden behind the
+    // bucketing
+    info->ms_prep = tm.on ? tm.ms(0, 1) - ms.grid - ms.fft - ms.screen : 0.0f;
+    info->ms_grid = ms.grid;
+    info->ms_fft = ms.fft;
+    info->ms_screen = ms.screen;
+}
+
+// The band zeroing of the first plane chunk (HBM writes) overlaps the
+// bucketing (bound by memory-side atomics): it runs on the auxiliary stream
+// after the call's earlier work on `st`; the first plane pass waits for it.
+static void zero_first_band(AuxWork &aux, const Plan &P) {
+    if (env_int("SDP_HIP_ZERO_OVERLAP", 1) == 0) return;
+    aux.start([&](hipStream_t s) { zero_band(P, std::min(P.g.nplanes, P.chunk_planes), s); });
+}
+
+// The invert's plane passes over the records P.recs, one per chunk of
+// resident planes: zero the band (a batch sequence: its `first` batch only;
+// not the chunk `aux` has zeroed), grid, and -- a batch sequence: on its
+// `last` batch only -- merge the core, FFT and screen the planes into `dirty`.
+static void invert_planes(const Plan &P, double *dirty, int64_t sx, int64_t sy, int accumulate,
+                          bool first, bool last, const double *tab, AuxWork &aux, StageMs &ms,
+                          hipStream_t st) {
+    const Geo &g = P.g;
+    for (int p_lo = 0; p_lo < g.nplanes; p_lo += P.chunk_planes) {
+        const int p_hi = std::min(g.nplanes, p_lo + P.chunk_planes);
+        const int np = p_hi - p_lo;
+        if (!aux.join() && first) zero_band(P, np, st);
+        {
+            StageTimer tg(st);
+            tg.mark();
+            if (P.f64) grid_f64(P, p_lo, p_hi, st);
+            else grid_f32(P, p_lo, p_hi, st);
+            SDP_HIP_CHECK(hipGetLastError());
+            tg.mark();
+            ms.grid += tg.ms(0, 1);
+        }
+        if (last) core_merge(P, 0, np, st);
+        for (int sb = 0; last && sb < np; sb += P.fft_planes) {
+            const int nb = std::min(P.fft_planes, np - sb);
+            StageTimer t2(st);
+            t2.mark();
+            fft_rows_y(P, sb, nb, HIPFFT_BACKWARD, st);
+            tr_grid_to_t(P, sb, nb, st);
+            xfft_screen_fwd(P, p_lo + sb, nb, dirty, sx, sy, (accumulate || p_lo + sb > 0) ? 1 : 0,
+                            tab, st, t2);
+            ms.fft += t2.ms(0, 1);
+            ms.screen += t2.ms(1, 2);
+        }
+    }
+    aux.join();  // (no plane pass ran)
+}
 
 static void ms2dirty(const Inputs &in, double *dirty, int64_t sx, int64_t sy,
                      sdp_hip_wgrid_info *info, hipStream_t st) {
@@ -6142,18 +6064,10 @@ static void ms2dirty(const Inputs &in, double *dirty, int64_t sx, int64_t sy,
         check_batch_seq(P, in, first);
     }
     const double *tab = phi_table(g.W, g.beta, st);
-    // the band zeroing of the first plane chunk (HBM writes) overlaps the
-    // bucketing (bound by memory-side atomics): it runs on the auxiliary
-    // stream after the call's earlier work on `st`; the gridding waits for it
+    AuxWork aux(st);
     // (single calls only: on C4's streamed batches it measured 1-2 % slower)
-    hipEvent_t zdone = nullptr;
     auto start_zero = [&] {
-        if (!(first && !batched && env_int("SDP_HIP_ZERO_OVERLAP", 1) != 0)) return;
-        hipStream_t aux = aux_stream();
-        stream_after(aux, st);
-        zero_band(P, std::min(g.nplanes, P.chunk_planes), aux);
-        SDP_HIP_CHECK(hipEventCreateWithFlags(&zdone, hipEventDisableTiming));
-        SDP_HIP_CHECK(hipEventRecord(zdone, aux));
+        if (first && !batched) zero_first_band(aux, P);
     };
     if (reuse) {
         start_zero();
@@ -6162,63 +6076,27 @@ static void ms2dirty(const Inputs &in, double *dirty, int64_t sx, int64_t sy,
         if (slots) SDP_HIP_CHECK(hipMemsetAsync(slots, 0, kSumSlots * sizeof(double), st));
         if (P.g.tiled) bucket_tiled(P, inx, true, st, true, nullptr, slots);
         else bucket_part(P, inx, true, st, true);
-        if (slots) k_sum_slots<<<1, 64, 0, st>>>(slots, in.x.sumwt);
+        if (slots) sum_slots(slots, in.x.sumwt, st);
     } else {
         bucket_all(P, inx, true, st, start_zero);
     }
     if (P.subsort) subsort_items(P, st);
     if (keep) keep_buckets(P, in);
-    const int accumulate = (in.flags & SDP_HIP_ACCUMULATE) ? 1 : 0;
-    float tgrid = 0, tfft = 0, tscr = 0;
-    for (int p_lo = 0; p_lo < g.nplanes; p_lo += P.chunk_planes) {
-        const int p_hi = std::min(g.nplanes, p_lo + P.chunk_planes);
-        const int np = p_hi - p_lo;
-        if (zdone) {
-            SDP_HIP_CHECK(hipStreamWaitEvent(st, zdone, 0));
-            SDP_HIP_CHECK(hipEventDestroy(zdone));
-            zdone = nullptr;
-        } else if (first) {
-            zero_band(P, np, st);
-        }
-        {
-            StageTimer tg(st);
-            tg.mark();
-#define SDP_LAUNCH_GRID(WW) launch_grid<WW>(P, p_lo, p_hi, st)
-            if (P.f64) grid_f64(P, p_lo, p_hi, st);
-            else SDP_W_DISPATCH(g.W, SDP_LAUNCH_GRID);
-#undef SDP_LAUNCH_GRID
-            SDP_HIP_CHECK(hipGetLastError());
-            tg.mark();
-            tgrid += tg.ms(0, 1);
-        }
-        if (last) core_merge(P, 0, np, st);
-        for (int sb = 0; last && sb < np; sb += P.fft_planes) {
-            const int nb = std::min(P.fft_planes, np - sb);
-            StageTimer t2(st);
-            t2.mark();
-            fft_rows_y(P, sb, nb, HIPFFT_BACKWARD, st);
-            tr_grid_to_t(P, sb, nb, st);
-            xfft_screen_fwd(P, p_lo + sb, nb, dirty, sx, sy,
-                            (accumulate || p_lo + sb > 0) ? 1 : 0, tab, st, t2);
-            tfft += t2.ms(0, 1);
-            tscr += t2.ms(1, 2);
-        }
-    }
-    if (zdone) {  // (no plane pass ran)
-        SDP_HIP_CHECK(hipStreamWaitEvent(st, zdone, 0));
-        SDP_HIP_CHECK(hipEventDestroy(zdone));
-    }
+    StageMs ms;
+    invert_planes(P, dirty, sx, sy, (in.flags & SDP_HIP_ACCUMULATE) ? 1 : 0, first, last, tab, aux,
+                  ms, st);
     if (batched && last) drop_batch_seq();
-    tm.mark();
-    fill_info(P, info);
-    if (info) {
-        // everything on the call's stream that is not gridding, FFT or screen:
-        // geometry, bucketing, band zeroing not hidden behind the bucketing
-        info->ms_prep = tm.on ? tm.ms(0, 1) - tgrid - tfft - tscr : 0.0f;
-        info->ms_grid = tgrid;
-        info->ms_fft = tfft;
-        info->ms_screen = tscr;
+    finish_info(P, tm, ms, info);
+}
+
+// image pol q of a pols call as a conversion: row q of the matrix, pol q's flags
+static void set_pol_row(VisExtra &x, const PolsSpec &ps, int q) {
+    x.conv = true;
+    for (int k = 0; k < 4; ++k) {
+        x.cre[k] = ps.cre[q][k];
+        x.cim[k] = ps.cim[q][k];
     }
+    x.fpol = q;
 }
 
 // All image pols of one invert_ng call in one bucketing (sdp_hip_ms2dirty_vis_pols):
@@ -6227,7 +6105,7 @@ static void ms2dirty(const Inputs &in, double *dirty, int64_t sx, int64_t sy,
 // image pol 0's call (its conversion row, weights and flag pol); `ps` holds
 // every pol's rows and the weights' pol stride, `dirty[q]` / `sumwt[q]` the
 // outputs.  Plans the fused pass does not cover (fp64, two-level-only or
-// large-grid plans) run the pols one call each, sharing a kept bucketing.
+// large-grid plans) run the pols one call each.
 static void ms2dirty_pols(const Inputs &in, PolsSpec ps, double *const *dirty, int64_t sx,
                           int64_t sy, double *const *sumwt, sdp_hip_wgrid_info *info,
                           hipStream_t st) {
@@ -6236,140 +6114,59 @@ static void ms2dirty_pols(const Inputs &in, PolsSpec ps, double *const *dirty, i
                 "vis must be complex64 or complex128");
     SDP_REQUIRE(ps.npo <= in.x.npv, "npol_img must not exceed npol_vis (pol q's flags mask its "
                                     "weights)");
-    auto per_pol = [&] {
+    // one ms2dirty call per pol; `share`: the first keeps its bucketing for
+    // the others
+    auto per_pol = [&](bool share) {
         for (int q = 0; q < ps.npo; ++q) {
             Inputs iq = in;
-            iq.x.conv = true;
-            for (int k = 0; k < 4; ++k) {
-                iq.x.cre[k] = ps.cre[q][k];
-                iq.x.cim[k] = ps.cim[q][k];
-            }
-            iq.x.fpol = q;
-            iq.wgt = static_cast<const char *>(ps.wgt) +
-                     q * ps.wps * (in.x.wgt_f64 ? sizeof(double) : sizeof(float));
-            iq.x.sumwt = sumwt[q];
-            iq.flags = (in.flags & ~(SDP_HIP_KEEP_BUCKETS | SDP_HIP_REUSE_BUCKETS)) |
-                       (ps.npo > 1 ? (q == 0 ? SDP_HIP_KEEP_BUCKETS : SDP_HIP_REUSE_BUCKETS) : 0);
-            ms2dirty(iq, dirty[q], sx, sy, q == ps.npo - 1 ? info : nullptr, st);
-        }
-    };
-    if (in.eps < 1.0e-7 && !(in.flags & SDP_HIP_FP32)) {
-        // (fp64: each pol its own two-level sort, as invert_ng runs them)
-        for (int q = 0; q < ps.npo; ++q) {
-            Inputs iq = in;
-            iq.x.conv = true;
-            for (int k = 0; k < 4; ++k) {
-                iq.x.cre[k] = ps.cre[q][k];
-                iq.x.cim[k] = ps.cim[q][k];
-            }
-            iq.x.fpol = q;
+            set_pol_row(iq.x, ps, q);
             iq.wgt = static_cast<const char *>(ps.wgt) +
                      q * ps.wps * (in.x.wgt_f64 ? sizeof(double) : sizeof(float));
             iq.x.sumwt = sumwt[q];
             iq.flags = in.flags & ~(SDP_HIP_KEEP_BUCKETS | SDP_HIP_REUSE_BUCKETS);
+            if (share && ps.npo > 1)
+                iq.flags |= q == 0 ? SDP_HIP_KEEP_BUCKETS : SDP_HIP_REUSE_BUCKETS;
             ms2dirty(iq, dirty[q], sx, sy, q == ps.npo - 1 ? info : nullptr, st);
         }
-        return;
-    }
+    };
+    // (fp64: each pol its own two-level sort, as invert_ng runs them)
+    if (in.eps < 1.0e-7 && !(in.flags & SDP_HIP_FP32)) return per_pol(false);
     SlotGuard slot(in.flags);
     StageTimer tm(st);
     tm.mark();
     Inputs inx = in;
-    inx.x.conv = true;
-    for (int k = 0; k < 4; ++k) {
-        inx.x.cre[k] = ps.cre[0][k];
-        inx.x.cim[k] = ps.cim[0][k];
-    }
-    inx.x.fpol = 0;
+    set_pol_row(inx.x, ps, 0);
     inx.x.all = true;         // every in-grid visibility: the bucketing holds for every pol
     inx.x.sumwt = nullptr;    // (the value pass sums every pol's weights)
     inx.flags = (in.flags & ~SDP_HIP_REUSE_BUCKETS) | SDP_HIP_KEEP_BUCKETS;  // single-level
     Plan P = plan_geometry(inx, true, st);
-    if (P.f64 || P.g.tiled || P.g.sub != kTileCell || !P.pad4 || P.subpad) {
-        per_pol();
-        return;
-    }
+    if (P.f64 || P.g.tiled || P.g.sub != kTileCell || !P.pad4 || P.subpad) return per_pol(true);
     setup_core(P);
-    const Geo &g = P.g;
-    const double *tab = phi_table(g.W, g.beta, st);
-    hipEvent_t zdone = nullptr;
-    auto start_zero = [&] {
-        if (env_int("SDP_HIP_ZERO_OVERLAP", 1) == 0) return;
-        hipStream_t aux = aux_stream();
-        stream_after(aux, st);
-        zero_band(P, std::min(g.nplanes, P.chunk_planes), aux);
-        SDP_HIP_CHECK(hipEventCreateWithFlags(&zdone, hipEventDisableTiming));
-        SDP_HIP_CHECK(hipEventRecord(zdone, aux));
-    };
+    const double *tab = phi_table(P.g.W, P.g.beta, st);
+    AuxWork aux(st);
     double *slots = scratch<double>("sumwt_slots_pols", 4 * kSumSlots);
     SDP_HIP_CHECK(hipMemsetAsync(slots, 0, 4 * kSumSlots * sizeof(double), st));
     for (int q = 0; q < ps.npo; ++q) ps.slots[q] = sumwt[q] ? slots + q * kSumSlots : nullptr;
-    bucket_part(P, inx, true, st, false, start_zero, &ps);
+    bucket_part(P, inx, true, st, false, [&] { zero_first_band(aux, P); }, &ps);
     for (int q = 0; q < ps.npo; ++q)
-        if (sumwt[q]) k_sum_slots<<<1, 64, 0, st>>>(ps.slots[q], sumwt[q]);
+        if (sumwt[q]) sum_slots(ps.slots[q], sumwt[q], st);
     read_part_meta(P, st);
-    const int accumulate = (in.flags & SDP_HIP_ACCUMULATE) ? 1 : 0;
-    float tgrid = 0, tfft = 0, tscr = 0;
+    StageMs ms;
     for (int q = 0; q < ps.npo; ++q) {
         P.recs = reinterpret_cast<VisRec *>(ps.recs[q]);
-        for (int p_lo = 0; p_lo < g.nplanes; p_lo += P.chunk_planes) {
-            const int p_hi = std::min(g.nplanes, p_lo + P.chunk_planes);
-            const int np = p_hi - p_lo;
-            if (zdone) {
-                SDP_HIP_CHECK(hipStreamWaitEvent(st, zdone, 0));
-                SDP_HIP_CHECK(hipEventDestroy(zdone));
-                zdone = nullptr;
-            } else {
-                zero_band(P, np, st);
-            }
-            {
-                StageTimer tg(st);
-                tg.mark();
-#define SDP_LAUNCH_GRID(WW) launch_grid<WW>(P, p_lo, p_hi, st)
-                SDP_W_DISPATCH(g.W, SDP_LAUNCH_GRID);
-#undef SDP_LAUNCH_GRID
-                SDP_HIP_CHECK(hipGetLastError());
-                tg.mark();
-                tgrid += tg.ms(0, 1);
-            }
-            core_merge(P, 0, np, st);
-            for (int sb = 0; sb < np; sb += P.fft_planes) {
-                const int nb = std::min(P.fft_planes, np - sb);
-                StageTimer t2(st);
-                t2.mark();
-                fft_rows_y(P, sb, nb, HIPFFT_BACKWARD, st);
-                tr_grid_to_t(P, sb, nb, st);
-                xfft_screen_fwd(P, p_lo + sb, nb, dirty[q], sx, sy,
-                                (accumulate || p_lo + sb > 0) ? 1 : 0, tab, st, t2);
-                tfft += t2.ms(0, 1);
-                tscr += t2.ms(1, 2);
-            }
-        }
+        invert_planes(P, dirty[q], sx, sy, (in.flags & SDP_HIP_ACCUMULATE) ? 1 : 0, true, true, tab,
+                      aux, ms, st);
     }
-    if (zdone) {
-        SDP_HIP_CHECK(hipStreamWaitEvent(st, zdone, 0));
-        SDP_HIP_CHECK(hipEventDestroy(zdone));
-    }
-    P.recs = reinterpret_cast<VisRec *>(ps.recs[0]);
-    tm.mark();
-    fill_info(P, info);
-    if (info) {
-        info->ms_prep = tm.on ? tm.ms(0, 1) - tgrid - tfft - tscr : 0.0f;
-        info->ms_grid = tgrid;
-        info->ms_fft = tfft;
-        info->ms_screen = tscr;
-    }
+    finish_info(P, tm, ms, info);
 }
 
-static void dirty2ms(const Inputs &in, const double *dirty, int64_t sx, int64_t sy, void *vis,
-                     sdp_hip_wgrid_info *info, hipStream_t st, const OutConv &oc = OutConv{},
-                     int npo = 1, const double *const *dirty_q = nullptr,
-                     const OutConv *oc_q = nullptr) {
-    // npo > 1 (sdp_hip_dirty2ms_vis_pols): image pol q is dirty_q[q] through
-    // the conversion column oc_q[q], into one output; the pols share the
-    // bucketing, each has its plane stage and degridding, and one write-back
-    // combines them (fp64: the degridder adds each pol itself)
-    auto img = [&](int q) { return npo > 1 ? dirty_q[q] : dirty; };
+// The predict of npo image pols img[q] through their conversions oc[q] into
+// one output (npo > 1: sdp_hip_dirty2ms_vis_pols): the pols share the
+// bucketing, each has its plane stage and degridding, and one write-back
+// combines them (fp64: the degridder adds each pol itself).
+static void dirty2ms(const Inputs &in, int npo, const double *const *img, const OutConv *oc,
+                     int64_t sx, int64_t sy, void *vis, sdp_hip_wgrid_info *info,
+                     hipStream_t st) {
     SDP_REQUIRE(in.vis_dtype == SDP_HIP_C64 || in.vis_dtype == SDP_HIP_C128,
                 "vis must be complex64 or complex128");
     SlotGuard slot(in.flags);
@@ -6380,40 +6177,20 @@ static void dirty2ms(const Inputs &in, const double *dirty, int64_t sx, int64_t 
     const double *tab = phi_table(g.W, g.beta, st);
     const int accumulate = (in.flags & SDP_HIP_ACCUMULATE) ? 1 : 0;
     const int64_t nvis = in.nrow * (int64_t)in.nchan;
-    OutConv ocz = oc;  // the visibility pols any image pol writes
-    if (npo > 1) {
-        ocz = oc_q[0];
-        for (int k = 0; k < ocz.npv; ++k) {
-            bool any = false;
-            for (int q = 0; q < npo; ++q) any |= oc_q[q].cre[k] != 0.0 || oc_q[q].cim[k] != 0.0;
-            ocz.cre[k] = any ? 1.0 : 0.0;
-            ocz.cim[k] = 0.0;
-        }
-    }
-    auto zero_vis = [&](hipStream_t s) {
-        if (accumulate || nvis <= 0) return;
-        if (in.vis_dtype == SDP_HIP_C128)
-            k_zero_vis<double2><<<grid1d(nvis, 256), 256, 0, s>>>(in.nrow, in.nchan,
-                                                                   (double2 *)vis, in.vrs,
-                                                                   in.vcs, ocz);
-        else
-            k_zero_vis<float2><<<grid1d(nvis, 256), 256, 0, s>>>(in.nrow, in.nchan, (float2 *)vis,
-                                                                  in.vrs, in.vcs, ocz);
-        SDP_HIP_CHECK(hipGetLastError());
-    };
     // all planes in one pass into plain contiguous c64 visibilities: the
     // degridder applies the record factor and writes each visibility once,
     // and on the single-level bucketing the rank pass zeroes the
     // visibilities no record reaches (no separate 1 GB zeroing pass on C2);
     // otherwise the output is zeroed first
-    const bool trivial_oc = oc.npv == 1 && oc.cre[0] == 1.0 && oc.cim[0] == 0.0;
+    const bool trivial_oc = oc[0].npv == 1 && oc[0].cre[0] == 1.0 && oc[0].cim[0] == 0.0;
     if (npo == 1 && P.chunk_planes == g.nplanes && !accumulate && in.vis_dtype != SDP_HIP_C128 &&
         trivial_oc && in.vcs == 1 && in.vrs == in.nchan && !P.f64) {
         P.vdirect = static_cast<float2 *>(vis);
         if (!g.tiled) P.zout = P.vdirect;
     }
+    // (every pol's conversion has the output's npv pols and pol stride)
     auto zero_vis_unless_fused = [&](hipStream_t s) {
-        if (!P.zout) zero_vis(s);
+        if (!P.zout && !accumulate) zero_vis(in, vis, oc[0], s);
     };
     // screens + FFTs of planes [p_lo, p_lo + np) into the grid
     std::vector<std::unique_ptr<StageTimer>> stage_t;
@@ -6438,16 +6215,14 @@ static void dirty2ms(const Inputs &in, const double *dirty, int64_t sx, int64_t 
     // slower count pass of that time, it had measured 15.6 vs 15.4 ms)
     const bool overlap = env_int("SDP_HIP_ZERO_OVERLAP", 1) != 0;
     const bool planes_aux = overlap && P.chunk_planes == g.nplanes;
-    hipEvent_t zdone = nullptr;
+    AuxWork aux(st);
     auto start_aux = [&] {
         if (!overlap) return;
-        hipStream_t aux = aux_stream();
-        stream_after(aux, st);
-        zero_vis_unless_fused(aux);
-        zero_band(P, std::min(g.nplanes, P.chunk_planes), aux);
-        if (planes_aux) plane_stage(0, g.nplanes, aux, img(0));
-        SDP_HIP_CHECK(hipEventCreateWithFlags(&zdone, hipEventDisableTiming));
-        SDP_HIP_CHECK(hipEventRecord(zdone, aux));
+        aux.start([&](hipStream_t s) {
+            zero_vis_unless_fused(s);
+            zero_band(P, std::min(g.nplanes, P.chunk_planes), s);
+            if (planes_aux) plane_stage(0, g.nplanes, s, img[0]);
+        });
     };
     if (!overlap) zero_vis_unless_fused(st);
     bucket_all(P, in, false, st, start_aux);
@@ -6463,93 +6238,102 @@ static void dirty2ms(const Inputs &in, const double *dirty, int64_t sx, int64_t 
                 hipMemsetAsync(accs[q], 0, std::max<int64_t>(nvis, 1) * sizeof(float2), st));
         }
     }
-    float2 *const acc = accs[0];
-    float tgrid = 0, tfft = 0, tscr = 0;
-    for (int q = 0; q < npo; ++q) {
-      const OutConv &ocq = npo > 1 ? oc_q[q] : oc;
-      float2 *const accq = accs[q];
-      for (int p_lo = 0; p_lo < g.nplanes; p_lo += P.chunk_planes) {
-        const int p_hi = std::min(g.nplanes, p_lo + P.chunk_planes);
-        const int np = p_hi - p_lo;
-        if (zdone) {
-            SDP_HIP_CHECK(hipStreamWaitEvent(st, zdone, 0));
-            SDP_HIP_CHECK(hipEventDestroy(zdone));
-            zdone = nullptr;
-            if (!planes_aux) plane_stage(p_lo, np, st, img(q));
-        } else {
-            zero_band(P, np, st);
-            plane_stage(p_lo, np, st, img(q));
+    StageMs ms;
+    for (int q = 0; q < npo; ++q)
+        for (int p_lo = 0; p_lo < g.nplanes; p_lo += P.chunk_planes) {
+            const int p_hi = std::min(g.nplanes, p_lo + P.chunk_planes);
+            const int np = p_hi - p_lo;
+            if (aux.join()) {
+                if (!planes_aux) plane_stage(p_lo, np, st, img[q]);
+            } else {
+                zero_band(P, np, st);
+                plane_stage(p_lo, np, st, img[q]);
+            }
+            StageTimer tg(st);
+            tg.mark();
+            if (P.f64) degrid_f64(P, p_lo, p_hi, vis, in.vis_dtype, in.vrs, in.vcs, 1, oc[q], st);
+            else degrid_f32(P, p_lo, p_hi, accs[q], st);
+            SDP_HIP_CHECK(hipGetLastError());
+            tg.mark();
+            ms.grid += tg.ms(0, 1);
         }
-        StageTimer tg(st);
-        tg.mark();
-#define SDP_LAUNCH_DEGRID(WW) launch_degrid<WW>(P, p_lo, p_hi, accq, st)
-        if (P.f64 && in.vis_dtype == SDP_HIP_C128)
-            degrid_f64<double2>(P, p_lo, p_hi, static_cast<double2 *>(vis), in.vrs, in.vcs, 1, ocq,
-                                st);
-        else if (P.f64)
-            degrid_f64<float2>(P, p_lo, p_hi, static_cast<float2 *>(vis), in.vrs, in.vcs, 1, ocq,
-                               st);
-        else
-            SDP_W_DISPATCH(g.W, SDP_LAUNCH_DEGRID);
-#undef SDP_LAUNCH_DEGRID
-        SDP_HIP_CHECK(hipGetLastError());
-        tg.mark();
-        tgrid += tg.ms(0, 1);
-      }
-    }
-    if (zdone) {  // (no plane pass ran)
-        SDP_HIP_CHECK(hipStreamWaitEvent(st, zdone, 0));
-        SDP_HIP_CHECK(hipEventDestroy(zdone));
-    }
+    aux.join();  // (no plane pass ran)
     for (auto &t : stage_t) {
-        tscr += t->ms(0, 1);
-        tfft += t->ms(1, 2);
+        ms.screen += t->ms(0, 1);
+        ms.fft += t->ms(1, 2);
     }
-    if (npo > 1 && !P.f64 && P.pt.nvis > 0) {
-        const unsigned nb = std::min<unsigned>(grid1d(P.pt.nvis, 256), 16384);
-        PolAccs pa;
-        for (int q = 0; q < npo; ++q) {
-            pa.a[q] = accs[q];
-            pa.oc[q] = oc_q[q];
-        }
-#define SDP_FIN(VT, N)                                                                     \
-    k_finalize_pols<VT, N><<<nb, 256, 0, st>>>(P.pt.nrec, in.nchan, P.recs, pa, (VT *)vis, \
-                                               in.vrs, in.vcs, accumulate)
-        if (in.vis_dtype == SDP_HIP_C128) {
-            if (npo == 2) SDP_FIN(double2, 2);
-            else if (npo == 3) SDP_FIN(double2, 3);
-            else SDP_FIN(double2, 4);
-        } else {
-            if (npo == 2) SDP_FIN(float2, 2);
-            else if (npo == 3) SDP_FIN(float2, 3);
-            else SDP_FIN(float2, 4);
-        }
-#undef SDP_FIN
-        SDP_HIP_CHECK(hipGetLastError());
-    } else if (!P.vdirect && !P.f64 && P.pt.nvis > 0) {
-        const unsigned nb = std::min<unsigned>(grid1d(P.pt.nvis, 256), 16384);
-        if (in.vis_dtype == SDP_HIP_C128)
-            k_finalize<double2><<<nb, 256, 0, st>>>(P.pt.nrec, in.nchan, P.recs, acc,
-                                                    (double2 *)vis, in.vrs, in.vcs, accumulate, oc);
-        else
-            k_finalize<float2><<<nb, 256, 0, st>>>(P.pt.nrec, in.nchan, P.recs, acc, (float2 *)vis,
-                                                   in.vrs, in.vcs, accumulate, oc);
-        SDP_HIP_CHECK(hipGetLastError());
-    }
-    tm.mark();
-    fill_info(P, info);
-    if (info) {
-        info->ms_prep = tm.on ? tm.ms(0, 1) - tgrid - tfft - tscr : 0.0f;
-        info->ms_grid = tgrid;
-        info->ms_fft = tfft;
-        info->ms_screen = tscr;
-    }
+    if (!P.vdirect && !P.f64) finalize_vis(P, in, npo, accs, oc, vis, accumulate, st);
+    finish_info(P, tm, ms, info);
 }
 
 }  // namespace wstack
 }  // namespace sdp
 
 using namespace sdp;
+
+// ---- what the C entry points share ---------------------------------------
+static wstack::Inputs make_inputs(const double *uvw, int64_t uvw_row_stride, const double *freq,
+                                  int nchan, int64_t nrow, const void *vis, int vis_dtype,
+                                  int64_t vis_row_stride, int64_t vis_chan_stride, const void *wgt,
+                                  int64_t wgt_row_stride, int64_t wgt_chan_stride, int npix_x,
+                                  int npix_y, double pixsize_x, double pixsize_y, double epsilon,
+                                  int do_wstacking, unsigned flags) {
+    return wstack::Inputs{uvw,         uvw_row_stride,  freq,           nchan,
+                          nrow,        vis,             vis_dtype,      vis_row_stride,
+                          vis_chan_stride, wgt,         wgt_row_stride, wgt_chan_stride,
+                          npix_x,      npix_y,          pixsize_x,      pixsize_y,
+                          epsilon,     do_wstacking,    flags};
+}
+
+// the visibility-side prologue's pol strides, weight type and flags
+static void set_vis_extra(wstack::VisExtra &x, int64_t vis_pol_stride, int npol_vis, int wgt_dtype,
+                          const void *vis_flags, int flag_bytes, int64_t flag_row_stride,
+                          int64_t flag_chan_stride, int64_t flag_pol_stride) {
+    x.vps = vis_pol_stride;
+    x.npv = npol_vis;
+    x.wgt_f64 = wgt_dtype == SDP_HIP_F64;
+    x.flags = vis_flags;
+    x.fbytes = vis_flags ? flag_bytes : 0;
+    x.frs = flag_row_stride;
+    x.fcs = flag_chan_stride;
+    x.fps = flag_pol_stride;
+}
+
+static void set_shift(wstack::VisExtra &x, const double *shift_lmn) {
+    if (!shift_lmn) return;
+    x.shift = true;
+    x.sl = shift_lmn[0];
+    x.sm = shift_lmn[1];
+    x.sn = shift_lmn[2];
+}
+
+// row `row` of the complex [.., npv] matrix pol_coeff as cre / cim; without a
+// matrix the unit row of pol `unit`
+static void pol_row(const double *pol_coeff, int row, int npv, int unit, double *cre,
+                    double *cim) {
+    for (int k = 0; k < npv; ++k) {
+        cre[k] = pol_coeff ? pol_coeff[2 * (row * npv + k)] : (k == unit ? 1.0 : 0.0);
+        cim[k] = pol_coeff ? pol_coeff[2 * (row * npv + k) + 1] : 0.0;
+    }
+}
+
+static wstack::OutConv out_conv(const double *pol_coeff, int row, int npol_vis,
+                                int64_t vis_pol_stride) {
+    wstack::OutConv oc;
+    oc.npv = npol_vis;
+    oc.vps = vis_pol_stride;
+    pol_row(pol_coeff, row, npol_vis, row, oc.cre, oc.cim);
+    return oc;
+}
+
+// sdp_hip_ms2dirty and sdp_hip_ms2dirty_batch (bounds) behind their argument checks
+static void bare_ms2dirty(wstack::Inputs in, int wgt_dtype, const double *bounds, double *dirty,
+                          int64_t dirty_stride_x, int64_t dirty_stride_y, void *stream,
+                          sdp_hip_wgrid_info *info) {
+    in.x.wgt_f64 = wstack::weight_is_f64(wgt_dtype);
+    in.bounds = bounds;
+    wstack::ms2dirty(in, dirty, dirty_stride_x, dirty_stride_y, info, as_stream(stream));
+}
 
 static int ms2dirty_vis_entry(const double *uvw, int64_t uvw_row_stride, const double *freq, int nchan,
                          int64_t nrow, const void *vis, int vis_dtype, int64_t vis_row_stride,
@@ -6573,35 +6357,20 @@ static int ms2dirty_vis_entry(const double *uvw, int64_t uvw_row_stride, const d
                     "weights must be f32 or f64");
         SDP_REQUIRE(vis_flags == nullptr || flag_bytes == 1 || flag_bytes == 4 || flag_bytes == 8,
                     "flag element size must be 1, 4 or 8 bytes");
-        wstack::Inputs in{uvw,         uvw_row_stride,  freq,           nchan,
-                          nrow,        vis,             vis_dtype,      vis_row_stride,
-                          vis_chan_stride, wgt,         wgt_row_stride, wgt_chan_stride,
-                          npix_x,      npix_y,          pixsize_x,      pixsize_y,
-                          epsilon,     do_wstacking,    flags};
+        wstack::Inputs in = make_inputs(uvw, uvw_row_stride, freq, nchan, nrow, vis, vis_dtype,
+                                        vis_row_stride, vis_chan_stride, wgt, wgt_row_stride,
+                                        wgt_chan_stride, npix_x, npix_y, pixsize_x, pixsize_y,
+                                        epsilon, do_wstacking, flags);
         in.bounds = bounds;
         wstack::VisExtra &x = in.x;
-        x.vps = vis_pol_stride;
-        x.npv = npol_vis;
-        x.wgt_f64 = wgt_dtype == SDP_HIP_F64;
-        x.flags = vis_flags;
-        x.fbytes = vis_flags ? flag_bytes : 0;
-        x.frs = flag_row_stride;
-        x.fcs = flag_chan_stride;
-        x.fps = flag_pol_stride;
+        set_vis_extra(x, vis_pol_stride, npol_vis, wgt_dtype, vis_flags, flag_bytes,
+                      flag_row_stride, flag_chan_stride, flag_pol_stride);
         x.fpol = pol;
         x.sumwt = sumwt;
-        if (shift_lmn) {
-            x.shift = true;
-            x.sl = shift_lmn[0];
-            x.sm = shift_lmn[1];
-            x.sn = shift_lmn[2];
-        }
+        set_shift(x, shift_lmn);
         if (pol_coeff) {
             x.conv = true;
-            for (int k = 0; k < npol_vis; ++k) {
-                x.cre[k] = pol_coeff[2 * k];
-                x.cim[k] = pol_coeff[2 * k + 1];
-            }
+            pol_row(pol_coeff, 0, npol_vis, 0, x.cre, x.cim);
         } else if (vis) {
             // no conversion: the image pol is the vis pol `pol`
             in.vis = static_cast<const char *>(vis) +
@@ -6646,13 +6415,11 @@ int sdp_hip_ms2dirty(const double *uvw, int64_t uvw_row_stride, const double *fr
     return guarded(errbuf, errbuf_len, [&] {
         SDP_REQUIRE(dirty != nullptr && freq != nullptr && (uvw != nullptr || nrow == 0),
                     "null pointer argument");
-        wstack::Inputs in{uvw,         uvw_row_stride,  freq,           nchan,
-                          nrow,        vis,             vis_dtype,      vis_row_stride,
-                          vis_chan_stride, wgt,         wgt_row_stride, wgt_chan_stride,
-                          npix_x,      npix_y,          pixsize_x,      pixsize_y,
-                          epsilon,     do_wstacking,    flags};
-        in.x.wgt_f64 = wstack::weight_is_f64(wgt_dtype);
-        wstack::ms2dirty(in, dirty, dirty_stride_x, dirty_stride_y, info, as_stream(stream));
+        bare_ms2dirty(make_inputs(uvw, uvw_row_stride, freq, nchan, nrow, vis, vis_dtype,
+                                  vis_row_stride, vis_chan_stride, wgt, wgt_row_stride,
+                                  wgt_chan_stride, npix_x, npix_y, pixsize_x, pixsize_y, epsilon,
+                                  do_wstacking, flags),
+                      wgt_dtype, nullptr, dirty, dirty_stride_x, dirty_stride_y, stream, info);
     });
 }
 
@@ -6671,14 +6438,11 @@ int sdp_hip_ms2dirty_batch(const double *uvw, int64_t uvw_row_stride, const doub
                     "null pointer argument");
         SDP_REQUIRE(dirty != nullptr || !(flags & SDP_HIP_BATCH_LAST),
                     "the last batch needs the dirty image");
-        wstack::Inputs in{uvw,         uvw_row_stride,  freq,           nchan,
-                          nrow,        vis,             vis_dtype,      vis_row_stride,
-                          vis_chan_stride, wgt,         wgt_row_stride, wgt_chan_stride,
-                          npix_x,      npix_y,          pixsize_x,      pixsize_y,
-                          epsilon,     do_wstacking,    flags};
-        in.x.wgt_f64 = wstack::weight_is_f64(wgt_dtype);
-        in.bounds = bounds;
-        wstack::ms2dirty(in, dirty, dirty_stride_x, dirty_stride_y, info, as_stream(stream));
+        bare_ms2dirty(make_inputs(uvw, uvw_row_stride, freq, nchan, nrow, vis, vis_dtype,
+                                  vis_row_stride, vis_chan_stride, wgt, wgt_row_stride,
+                                  wgt_chan_stride, npix_x, npix_y, pixsize_x, pixsize_y, epsilon,
+                                  do_wstacking, flags),
+                      wgt_dtype, bounds, dirty, dirty_stride_x, dirty_stride_y, stream, info);
     });
 }
 
@@ -6769,39 +6533,22 @@ int sdp_hip_ms2dirty_vis_pols(const double *uvw, int64_t uvw_row_stride, const d
         SDP_REQUIRE(!(flags & (SDP_HIP_KEEP_BUCKETS | SDP_HIP_REUSE_BUCKETS | SDP_HIP_BATCH_FIRST |
                                SDP_HIP_BATCH_LAST)),
                     "a pols call keeps, reuses or batches nothing");
-        wstack::Inputs in{uvw,         uvw_row_stride,  freq,           nchan,
-                          nrow,        vis,             vis_dtype,      vis_row_stride,
-                          vis_chan_stride, wgt,         wgt_row_stride, wgt_chan_stride,
-                          npix_x,      npix_y,          pixsize_x,      pixsize_y,
-                          epsilon,     do_wstacking,    flags};
-        wstack::VisExtra &x = in.x;
-        x.vps = vis_pol_stride;
-        x.npv = npol_vis;
-        x.wgt_f64 = wgt_dtype == SDP_HIP_F64;
-        x.flags = vis_flags;
-        x.fbytes = vis_flags ? flag_bytes : 0;
-        x.frs = flag_row_stride;
-        x.fcs = flag_chan_stride;
-        x.fps = flag_pol_stride;
-        if (shift_lmn) {
-            x.shift = true;
-            x.sl = shift_lmn[0];
-            x.sm = shift_lmn[1];
-            x.sn = shift_lmn[2];
-        }
+        wstack::Inputs in = make_inputs(uvw, uvw_row_stride, freq, nchan, nrow, vis, vis_dtype,
+                                        vis_row_stride, vis_chan_stride, wgt, wgt_row_stride,
+                                        wgt_chan_stride, npix_x, npix_y, pixsize_x, pixsize_y,
+                                        epsilon, do_wstacking, flags);
+        set_vis_extra(in.x, vis_pol_stride, npol_vis, wgt_dtype, vis_flags, flag_bytes,
+                      flag_row_stride, flag_chan_stride, flag_pol_stride);
+        set_shift(in.x, shift_lmn);
         wstack::PolsSpec ps;
         ps.npo = npol_img;
-        for (int q = 0; q < npol_img; ++q)
-            for (int k = 0; k < npol_vis; ++k) {
-                ps.cre[q][k] = pol_coeff ? pol_coeff[2 * (q * npol_vis + k)] : (q == k ? 1.0 : 0.0);
-                ps.cim[q][k] = pol_coeff ? pol_coeff[2 * (q * npol_vis + k) + 1] : 0.0;
-            }
         ps.wgt = wgt;
         ps.wrs = wgt_row_stride;
         ps.wcs = wgt_chan_stride;
         ps.wps = wgt_pol_stride;
         double *outs[4] = {}, *sums[4] = {};
         for (int q = 0; q < npol_img; ++q) {
+            pol_row(pol_coeff, q, npol_vis, q, ps.cre[q], ps.cim[q]);
             outs[q] = dirty + q * dirty_stride_pol;
             sums[q] = sumwt ? sumwt + q * sumwt_stride : nullptr;
         }
@@ -6847,13 +6594,13 @@ int sdp_hip_dirty2ms(const double *uvw, int64_t uvw_row_stride, const double *fr
         SDP_REQUIRE(dirty != nullptr && freq != nullptr && vis != nullptr &&
                         (uvw != nullptr || nrow == 0),
                     "null pointer argument");
-        wstack::Inputs in{uvw,         uvw_row_stride,  freq,           nchan,
-                          nrow,        nullptr,         vis_dtype,      vis_row_stride,
-                          vis_chan_stride, wgt,         wgt_row_stride, wgt_chan_stride,
-                          npix_x,      npix_y,          pixsize_x,      pixsize_y,
-                          epsilon,     do_wstacking,    flags};
+        wstack::Inputs in = make_inputs(uvw, uvw_row_stride, freq, nchan, nrow, nullptr, vis_dtype,
+                                        vis_row_stride, vis_chan_stride, wgt, wgt_row_stride,
+                                        wgt_chan_stride, npix_x, npix_y, pixsize_x, pixsize_y,
+                                        epsilon, do_wstacking, flags);
         in.x.wgt_f64 = wstack::weight_is_f64(wgt_dtype);
-        wstack::dirty2ms(in, dirty, dirty_stride_x, dirty_stride_y, vis, info,
+        const wstack::OutConv oc;
+        wstack::dirty2ms(in, 1, &dirty, &oc, dirty_stride_x, dirty_stride_y, vis, info,
                          as_stream(stream));
     });
 }
@@ -6871,26 +6618,13 @@ int sdp_hip_dirty2ms_vis(const double *uvw, int64_t uvw_row_stride, const double
                         (uvw != nullptr || nrow == 0),
                     "null pointer argument");
         SDP_REQUIRE(npol_vis >= 1 && npol_vis <= 4, "npol_vis must be 1..4");
-        wstack::Inputs in{uvw,         uvw_row_stride,  freq,           nchan,
-                          nrow,        nullptr,         vis_dtype,      vis_row_stride,
-                          vis_chan_stride, nullptr,     0,              0,
-                          npix_x,      npix_y,          pixsize_x,      pixsize_y,
-                          epsilon,     do_wstacking,    flags};
-        if (shift_lmn) {
-            in.x.shift = true;
-            in.x.sl = shift_lmn[0];
-            in.x.sm = shift_lmn[1];
-            in.x.sn = shift_lmn[2];
-        }
-        wstack::OutConv oc;
-        oc.npv = npol_vis;
-        oc.vps = vis_pol_stride;
-        for (int k = 0; k < npol_vis; ++k) {
-            oc.cre[k] = pol_coeff ? pol_coeff[2 * k] : (k == 0 ? 1.0 : 0.0);
-            oc.cim[k] = pol_coeff ? pol_coeff[2 * k + 1] : 0.0;
-        }
-        wstack::dirty2ms(in, dirty, dirty_stride_x, dirty_stride_y, vis, info, as_stream(stream),
-                         oc);
+        wstack::Inputs in = make_inputs(uvw, uvw_row_stride, freq, nchan, nrow, nullptr, vis_dtype,
+                                        vis_row_stride, vis_chan_stride, nullptr, 0, 0, npix_x,
+                                        npix_y, pixsize_x, pixsize_y, epsilon, do_wstacking, flags);
+        set_shift(in.x, shift_lmn);
+        const wstack::OutConv oc = out_conv(pol_coeff, 0, npol_vis, vis_pol_stride);
+        wstack::dirty2ms(in, 1, &dirty, &oc, dirty_stride_x, dirty_stride_y, vis, info,
+                         as_stream(stream));
     });
 }
 
@@ -6910,30 +6644,18 @@ int sdp_hip_dirty2ms_vis_pols(const double *uvw, int64_t uvw_row_stride, const d
                     "null pointer argument");
         SDP_REQUIRE(npol_vis >= 1 && npol_vis <= 4, "npol_vis must be 1..4");
         SDP_REQUIRE(npol_img >= 1 && npol_img <= 4, "npol_img must be 1..4");
-        wstack::Inputs in{uvw,         uvw_row_stride,  freq,           nchan,
-                          nrow,        nullptr,         vis_dtype,      vis_row_stride,
-                          vis_chan_stride, nullptr,     0,              0,
-                          npix_x,      npix_y,          pixsize_x,      pixsize_y,
-                          epsilon,     do_wstacking,    flags};
-        if (shift_lmn) {
-            in.x.shift = true;
-            in.x.sl = shift_lmn[0];
-            in.x.sm = shift_lmn[1];
-            in.x.sn = shift_lmn[2];
-        }
+        wstack::Inputs in = make_inputs(uvw, uvw_row_stride, freq, nchan, nrow, nullptr, vis_dtype,
+                                        vis_row_stride, vis_chan_stride, nullptr, 0, 0, npix_x,
+                                        npix_y, pixsize_x, pixsize_y, epsilon, do_wstacking, flags);
+        set_shift(in.x, shift_lmn);
         wstack::OutConv ocs[4];
         const double *imgs[4] = {};
         for (int q = 0; q < npol_img; ++q) {
-            ocs[q].npv = npol_vis;
-            ocs[q].vps = vis_pol_stride;
-            for (int k = 0; k < npol_vis; ++k) {
-                ocs[q].cre[k] = pol_coeff ? pol_coeff[2 * (q * npol_vis + k)] : (k == q ? 1.0 : 0.0);
-                ocs[q].cim[k] = pol_coeff ? pol_coeff[2 * (q * npol_vis + k) + 1] : 0.0;
-            }
+            ocs[q] = out_conv(pol_coeff, q, npol_vis, vis_pol_stride);
             imgs[q] = dirty + q * dirty_stride_pol;
         }
-        wstack::dirty2ms(in, dirty, dirty_stride_x, dirty_stride_y, vis, info, as_stream(stream),
-                         ocs[0], npol_img, imgs, ocs);
+        wstack::dirty2ms(in, npol_img, imgs, ocs, dirty_stride_x, dirty_stride_y, vis, info,
+                         as_stream(stream));
     });
 }
 

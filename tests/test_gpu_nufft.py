@@ -240,6 +240,106 @@ def test_plane_chunking_matches_resident(bucket, monkeypatch):
     assert rel_rms(vpart.cpu().numpy(), vfull.cpu().numpy()) < 1e-6
 
 
+# linear -> stokesIQUV rows (invert) and stokesIQUV -> linear columns (predict)
+_POLS_CONV = [[1, 0, 0, 1], [1, 0, 0, -1], [0, 1, 1, 0], [0, -1j, 1j, 0]]
+_POLS_COLS = [[1, 0, 0, 1], [1, 0, 0, -1], [0, 1, 1, 0], [0, 1j, -1j, 0]]
+
+
+def _pols_problem(seed, nrow, nchan, npix=128):
+    """The inputs of test_pols_call_matches_per_pol_calls (seed 72: 5,000 rows
+    x 6 channels) and test_predict_pols_call_matches_per_pol_calls (seed 73:
+    4,000 x 5): 4 pols, 128^2 image, epsilon 1e-5."""
+    rng = np.random.default_rng(seed)
+    freq = np.linspace(1.0e9, 1.2e9, nchan)
+    umax = 3000.0
+    uvw_h = rng.uniform(-1, 1, (nrow, 3)) * umax * orc.C_LIGHT / freq.max()
+    uvw_h[:, 2] *= 0.3
+    vis = rng.normal(size=(nrow, nchan, 4)) + 1j * rng.normal(size=(nrow, nchan, 4))
+    flags = (rng.uniform(size=(nrow, nchan, 4)) < 0.2).astype(np.int8)
+    wgt = rng.uniform(0.5, 2.0, (nrow, nchan, 4))
+    wgt[: nrow // 3, :, 0] = 0.0
+    imgs = rng.normal(size=(4, npix, npix))
+    cell = 0.35 / umax
+    return dict(uvw=T(uvw_h), freq=T(freq), vis=T(vis, torch.complex64), flags=T(flags),
+                wgt=T(wgt), imgs=T(imgs), args=(npix, npix, cell, cell, 1e-5, True), cell=cell)
+
+
+def _invert_pols(kernels, p):
+    sw = torch.zeros(4, dtype=torch.float64, device=dev())
+    out, info = kernels.ms2dirty_vis_pols(p["uvw"], p["freq"], p["vis"], p["wgt"], p["flags"],
+                                          _POLS_CONV, *p["args"], flip_uw=True, sumwt=sw)
+    return out.cpu().numpy(), sw.cpu().numpy(), info
+
+
+def _predict_pols(kernels, p):
+    out = torch.full_like(p["vis"], float("nan"))
+    _, info = kernels.dirty2ms_vis_pols(p["uvw"], p["freq"], p["imgs"], out, _POLS_COLS, p["cell"],
+                                        p["cell"], 1e-5, True, flip_uw=True)
+    return out.cpu().numpy(), info
+
+
+def test_pols_calls_plane_chunking_matches_resident(monkeypatch):
+    """The all-pols invert and predict (sdp_hip_ms2dirty_vis_pols,
+    sdp_hip_dirty2ms_vis_pols) under a grid budget that forces plane chunks
+    equal their all-planes-resident runs: images and visibilities to 1e-6
+    relative RMS (the bound of test_plane_chunking_matches_resident for the
+    same comparison), weight sums to 1e-12.  A plane-chunked invert is planned
+    without the Hermitian fold (plan_geometry), and at epsilon 1e-5 the folded
+    and the unfolded plan differ by the NUFFT's own approximation error
+    (measured 4.9e-6 here), so both runs are planned unfolded: the comparison
+    is of the chunking alone."""
+    from ska_sdp_func_python_amd import kernels
+    monkeypatch.setenv("SDP_HIP_HFOLD", "0")
+    pi, pp = _pols_problem(72, 5000, 6), _pols_problem(73, 4000, 5)
+    img_full, sw_full, inf_i = _invert_pols(kernels, pi)
+    vis_full, inf_p = _predict_pols(kernels, pp)
+    monkeypatch.setenv("SDP_HIP_GRID_BUDGET_GB", "0.0001")
+    img_part, sw_part, inf_i2 = _invert_pols(kernels, pi)
+    vis_part, inf_p2 = _predict_pols(kernels, pp)
+    print("planes", inf_i["nplanes"], inf_p["nplanes"], "chunks", inf_i2["plane_chunk"],
+          inf_p2["plane_chunk"])
+    assert inf_i["nplanes"] > 2 and inf_p["nplanes"] > 2
+    assert inf_i2["plane_chunk"] < inf_i2["nplanes"]
+    assert inf_p2["plane_chunk"] < inf_p2["nplanes"]
+    print("rel rms", [rel_rms(img_part[q], img_full[q]) for q in range(4)],
+          rel_rms(vis_part, vis_full))
+    for q in range(4):
+        assert rel_rms(img_part[q], img_full[q]) < 1e-6, q
+        assert abs(sw_part[q] - sw_full[q]) <= 1e-12 * abs(sw_full[q]), q
+    assert rel_rms(vis_part, vis_full) < 1e-6
+
+
+def test_stage_timings_reach_info():
+    """With sdp_hip_set_stage_timing on, the four ms_* fields of the info are
+    set by a plain invert, an all-pols invert and an all-pols predict: finite,
+    gridding and plane stages positive.  The inverts' stage timers nest on one
+    stream, so their prep (the outer interval's remainder) is positive too;
+    the predict's plane stage runs on the aux stream, so its remainder carries
+    no sign guarantee.  With timing off all four are 0."""
+    from ska_sdp_func_python_amd import kernels
+    pi, pp = _pols_problem(72, 5000, 6), _pols_problem(73, 4000, 5)
+    fields = ("ms_prep", "ms_grid", "ms_fft", "ms_screen")
+
+    def runs():
+        _, one = kernels.ms2dirty(pi["uvw"], pi["freq"], pi["vis"][:, :, 0].contiguous(),
+                                  pi["wgt"][:, :, 1].contiguous(), *pi["args"], flip_uw=True)
+        return one, _invert_pols(kernels, pi)[2], _predict_pols(kernels, pp)[1]
+
+    kernels.set_stage_timing(True)
+    try:
+        timed = runs()
+    finally:
+        kernels.set_stage_timing(False)
+    for k, info in enumerate(timed):
+        print(k, {f: info[f] for f in fields})
+        assert all(np.isfinite(info[f]) for f in fields), (k, info)
+        assert info["ms_grid"] > 0 and info["ms_fft"] + info["ms_screen"] > 0, (k, info)
+        if k < 2:
+            assert info["ms_prep"] > 0, (k, info)
+    for k, info in enumerate(runs()):
+        assert all(info[f] == 0 for f in fields), (k, info)
+
+
 @pytest.mark.parametrize("fft_planes,budget", [("2", None), ("3", "0.002")])
 def test_fft_batches_match_single_batch(fft_planes, budget, monkeypatch):
     """The per-plane FFT / w-screen stages run in batches of fft_planes planes
