@@ -94,3 +94,83 @@ def test_dft_c128_output_is_fp64_exact():
     b = kernels.dft_point(*args, freq=torch.as_tensor(freq, device=dev))
     assert rel_rms(a.cpu().numpy(), ref) < 1e-11
     assert rel_rms(b.cpu().numpy(), ref) < 2e-6
+
+
+# k_dft_mfma works in tiles of 16 rows x 16 components; a workgroup covers
+# 256 / 128 / 64 rows for npol 1 / 2 / 4 and stages components in chunks of 256.
+# (nrow, ncomp): rows below one tile, one short of a tile, one past the
+# workgroup of npol 4 and of npol 1; components padded to 16, exactly one chunk
+# and a chunk restart with a 1-component tail.  Every nrow and every ncomp
+# meets every npol, output type, uvw form and flux layout.
+_TILE_EDGES = [(1, 257), (15, 17), (65, 256), (257, 1)]
+_SENTINEL = complex(-7.0e30, 3.0e30)
+_GUARD_ROWS = 256  # the largest workgroup's rows: what a wrong row guard could reach
+
+
+def _tile_problem(nrow, ncomp, npol, fnchan):
+    """The generator and scales of test_dft_c128_output_is_fp64_exact, 2
+    channels, per-channel fluxes that differ when fnchan = 2."""
+    rng = np.random.default_rng(1000 * nrow + ncomp)
+    freq = np.array([1.0e9, 1.4e9])
+    uvw = rng.normal(0, 3e4, (nrow, 3))
+    lm = rng.uniform(-0.02, 0.02, (ncomp, 2))
+    dc = np.concatenate([lm, (np.sqrt(1 - (lm ** 2).sum(1)) - 1)[:, None]], 1)
+    flux = (rng.uniform(0.1, 2, (ncomp, fnchan, npol)) +
+            1j * rng.uniform(-0.1, 0.1, (ncomp, fnchan, npol)))
+    uvwl = uvw[:, None, :] * (freq / 299792458.0)[None, :, None]
+    ph = np.exp(-2j * np.pi * np.einsum("rfs,cs->rfc", uvwl, dc))
+    ref = np.einsum("rfc,cfp->rfp", ph, np.broadcast_to(flux, (ncomp, 2, npol)))
+    return dc, flux, uvw, uvwl, freq, ref
+
+
+@pytest.mark.parametrize("nrow,ncomp", _TILE_EDGES)
+@pytest.mark.parametrize("npol", [1, 2, 4])
+@pytest.mark.parametrize("vdt", [torch.complex64, torch.complex128])
+@pytest.mark.parametrize("metres", [True, False])
+@pytest.mark.parametrize("fnchan", [1, 2])
+def test_dft_tile_edges(nrow, ncomp, npol, vdt, metres, fnchan):
+    """Every k_dft_mfma instantiation (npol 1, 2, 4 x complex64 / complex128
+    output x metres / wavelengths) at sizes chosen for their position
+    relative to its tiles, against the direct fp64 sum: 1e-11 (complex128) and
+    2e-6 (complex64), the file's tolerances.  The output starts as a sentinel:
+    every element must be written, and no row past nrow."""
+    from ska_sdp_func_python_amd import kernels
+    dev = torch.device("cuda:0")
+    dc, flux, uvw, uvwl, freq, ref = _tile_problem(nrow, ncomp, npol, fnchan)
+    buf = torch.full((nrow + _GUARD_ROWS, 2, npol), _SENTINEL, dtype=vdt, device=dev)
+    t = lambda a: torch.as_tensor(a, device=dev)
+    if metres:
+        kernels.dft_point(t(dc), t(flux), t(uvw), freq=t(freq), out=buf[:nrow])
+    else:
+        kernels.dft_point(t(dc), t(flux), t(uvwl), out=buf[:nrow])
+    got = buf.cpu().numpy()
+    sentinel = np.asarray(_SENTINEL).astype(got.dtype)
+    assert np.all(got[nrow:] == sentinel), "rows past nrow were written"
+    assert not np.any(got[:nrow] == sentinel), "output elements left unwritten"
+    e = rel_rms(got[:nrow], ref)
+    print(f"\ndft tile edges nrow {nrow} ncomp {ncomp} npol {npol} {vdt} metres {metres} "
+          f"flux chans {fnchan}: rel RMS {e:.2e}")
+    assert e < (1e-11 if vdt == torch.complex128 else 2e-6)
+
+
+@pytest.mark.parametrize("npol", [1, 2, 4])
+@pytest.mark.parametrize("vdt", [torch.complex64, torch.complex128])
+@pytest.mark.parametrize("metres", [True, False])
+def test_dft_no_components_writes_zeros(npol, vdt, metres):
+    """ncomp = 0: the output is written as exact zeros (65 rows: one past the
+    workgroup of npol 4), and nothing past nrow."""
+    from ska_sdp_func_python_amd import kernels
+    dev = torch.device("cuda:0")
+    nrow = 65
+    _, _, uvw, uvwl, freq, _ = _tile_problem(nrow, 1, npol, 1)
+    dc = torch.zeros((0, 3), dtype=torch.float64, device=dev)
+    flux = torch.zeros((0, 1, npol), dtype=torch.complex128, device=dev)
+    buf = torch.full((nrow + _GUARD_ROWS, 2, npol), _SENTINEL, dtype=vdt, device=dev)
+    if metres:
+        kernels.dft_point(dc, flux, torch.as_tensor(uvw, device=dev),
+                          freq=torch.as_tensor(freq, device=dev), out=buf[:nrow])
+    else:
+        kernels.dft_point(dc, flux, torch.as_tensor(uvwl, device=dev), out=buf[:nrow])
+    got = buf.cpu().numpy()
+    assert np.all(got[:nrow] == 0)
+    assert np.all(got[nrow:] == np.asarray(_SENTINEL).astype(got.dtype))
