@@ -565,6 +565,48 @@ int sdp_hip_taper(int64_t nrow, int nchan, int npol, const double *uvw,
                   int kind, double param, double *imaging_weight, void *stream,
                   char *errbuf, size_t errbuf_len);
 
+/*
+ * CLEAN minor cycles on one image plane, replacing the numpy loops of the
+ * reference's hogbom (src/ska_sdp_func_python/image/cleaners.py:23-133) and
+ * msclean (:403-452, with find_max_abs_stack :565-610).  Everything is fp64
+ * and evaluated in the reference's order without contraction.
+ *   res            [nscales, ny, nx], updated in place: the residual (hogbom,
+ *                  nscales 1) or the scale-convolved residual stack
+ *   psf            [nscales, nscales, psf_ny, psf_nx]: the PSF (hogbom) or
+ *                  its scale cross terms; pixel (psf_ny/2, psf_nx/2) lands on
+ *                  the peak, the patch is [peak - n/2, peak + n/2) clipped
+ *   window         [nscales, ny, nx] or NULL: multiplies the search value
+ *   sensitivity    [ny, nx] or NULL (msclean only): the search uses
+ *                  resid * sens^2, the comparison across scales resid * sens
+ *   coupling_diag  [nscales] host doubles (msclean; NULL for hogbom)
+ *   scale_kernels  [nscales, psf_ny, psf_nx] (msclean; NULL for hogbom):
+ *                  added into comps, times gain * mval, on the patch
+ *   scale_extent   every scale kernel is zero further than this many pixels
+ *                  from (psf_ny/2, psf_nx/2), so that only that part of the
+ *                  patch is visited for comps; <= 0: the whole patch
+ *   comps          [ny, nx], accumulated into
+ *   absthresh      max(thresh, fracthresh * max|.|); cycles stop below
+ *                  0.9 * absthresh (hogbom: tested after the subtraction and
+ *                  that cycle counts; msclean: before, and on mval == 0)
+ * The peak is the first maximum in row-major order, the lower scale on a tie.
+ * *niter_done is the reference's iteration count, *stop_reason one of
+ * SDP_HIP_CLEAN_STOP_*.  The call returns after the last cycle has run.
+ */
+#define SDP_HIP_CLEAN_HOGBOM 0
+#define SDP_HIP_CLEAN_MSCLEAN 1
+#define SDP_HIP_CLEAN_STOP_NITER 0
+#define SDP_HIP_CLEAN_STOP_THRESHOLD 1
+#define SDP_HIP_CLEAN_STOP_ZERO 2
+int sdp_hip_clean_plane(int algorithm, int nscales, int ny, int nx,
+                        int psf_ny, int psf_nx, double *res, const double *psf,
+                        const double *window, const double *sensitivity,
+                        const double *coupling_diag,
+                        const double *scale_kernels, int scale_extent,
+                        double *comps, double gain, double pmax,
+                        double absthresh, int niter,
+                        int *niter_done, int *stop_reason, void *stream,
+                        char *errbuf, size_t errbuf_len);
+
 #ifdef __cplusplus
 }
 #endif

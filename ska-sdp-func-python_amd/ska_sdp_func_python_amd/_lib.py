@@ -35,6 +35,9 @@ SDP_HIP_FP32 = 64
 SDP_HIP_W_SLAB = 128
 SDP_HIP_SLOT1 = 256
 
+SDP_HIP_CLEAN_HOGBOM = 0
+SDP_HIP_CLEAN_MSCLEAN = 1
+
 c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
 c_dbl = ctypes.c_double
@@ -185,6 +188,12 @@ SIGNATURES = {
         c_int, c_int, c_dbl, c_vp, c_int, c_vp, c_vp] + _ERR,
     "sdp_hip_taper": [
         c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_dbl, c_vp, c_vp] + _ERR,
+    "sdp_hip_clean_plane": [
+        c_int, c_int, c_int, c_int, c_int, c_int,   # algorithm, nscales, ny, nx, psf_ny, psf_nx
+        c_vp, c_vp, c_vp, c_vp,                     # res, psf, window, sensitivity
+        c_vp, c_vp, c_int, c_vp,                    # coupling_diag (host), scale_kernels, extent, comps
+        c_dbl, c_dbl, c_dbl, c_int,                 # gain, pmax, absthresh, niter
+        ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_vp] + _ERR,
 }
 
 _lock = threading.Lock()

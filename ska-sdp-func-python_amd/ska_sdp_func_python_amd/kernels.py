@@ -902,3 +902,52 @@ def apply_gains(vis, weight, flags, use_flags, ant1, ant2, time_row, gain, inver
               _ptr(time_row), _ptr(gain), nrow_g, nants, nchan_g, nrec, int(bool(inverse)),
               _stream(vis.device))
     return vis, weight
+
+
+# ---- CLEAN minor cycles (sdp_hip_clean_plane) --------------------------------
+CLEAN_STOP = {0: "niter", 1: "threshold", 2: "zero"}
+
+
+def _f64_plane(t, name, shape):
+    _on_gpu(t, name)
+    if t.dtype != torch.float64 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must be a contiguous float64 device tensor of shape {tuple(shape)}")
+    return t
+
+
+def clean_plane(algorithm, res, psf, comps, gain, pmax, absthresh, niter, window=None,
+                sensitivity=None, coupling_diag=None, scale_kernels=None, scale_extent=0):
+    """Up to ``niter`` CLEAN minor cycles of one plane, in place on device f64:
+    ``res`` [S, ny, nx] (the residual; msclean: the scale-convolved stack),
+    ``psf`` [S, S, py, px] (msclean: the scale cross terms), ``comps``
+    [ny, nx]; optional ``window`` [S, ny, nx]; msclean also takes
+    ``sensitivity`` [ny, nx], ``coupling_diag`` (S host floats) and
+    ``scale_kernels`` [S, py, px], which ``scale_extent`` > 0 declares zero
+    further than that many pixels from (py // 2, px // 2).  ``algorithm``
+    "hogbom" (S = 1) or "msclean".  Returns (cycles run, "niter" | "threshold" | "zero")."""
+    if algorithm not in ("hogbom", "msclean"):
+        raise ValueError(f"unknown clean algorithm {algorithm}")
+    ms = algorithm == "msclean"
+    _on_gpu(res, "res")
+    if res.dim() != 3 or psf.dim() != 4:
+        raise ValueError("res must be [S, ny, nx] and psf [S, S, py, px]")
+    ns, ny, nx = res.shape
+    pny, pnx = psf.shape[2:]
+    _f64_plane(res, "res", (ns, ny, nx))
+    _f64_plane(psf, "psf", (ns, ns, pny, pnx))
+    _f64_plane(comps, "comps", (ny, nx))
+    if window is not None:
+        _f64_plane(window, "window", (ns, ny, nx))
+    if sensitivity is not None:
+        _f64_plane(sensitivity, "sensitivity", (ny, nx))
+    cd = None
+    if ms:
+        _f64_plane(scale_kernels, "scale_kernels", (ns, pny, pnx))
+        cd = (ctypes.c_double * ns)(*[float(c) for c in coupling_diag])
+    done, reason = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.call("sdp_hip_clean_plane",
+              _lib.SDP_HIP_CLEAN_MSCLEAN if ms else _lib.SDP_HIP_CLEAN_HOGBOM, ns, ny, nx, pny,
+              pnx, _ptr(res), _ptr(psf), _ptr(window), _ptr(sensitivity), cd,
+              _ptr(scale_kernels if ms else None), int(scale_extent), _ptr(comps), float(gain), float(pmax), float(absthresh), int(niter),
+              ctypes.byref(done), ctypes.byref(reason), _stream(res.device))
+    return done.value, CLEAN_STOP[reason.value]
