@@ -607,6 +607,56 @@ int sdp_hip_clean_plane(int algorithm, int nscales, int ny, int nx,
                         int *niter_done, int *stop_reason, void *stream,
                         char *errbuf, size_t errbuf_len);
 
+/*
+ * Multi-scale multi-frequency CLEAN minor cycles on one polarisation (Rau &
+ * Cornwell 2011, Algorithm 1), replacing the numpy loop of the reference's
+ * msmfsclean (src/ska_sdp_func_python/image/cleaners.py:831-876, with
+ * find_global_optimum :901-974, the two updates :977-1031, the principal
+ * solution :1107-1121 and find_optimum_scale_zero_moment :1124-1157).
+ * Everything is fp64, evaluated without contraction in the left-to-right
+ * order numpy's einsum takes.  nscales <= 16, nmoment <= 4.
+ *   smresidual     [nscales, nmoment, ny, nx], updated in place
+ *   m_model        [nmoment, ny, nx], accumulated into
+ *   ssmmpsf        [nscales, nscales, 2 * nmoment - 1, psf_ny, psf_nx]:
+ *                  plane k is the reference's ssmmpsf[s, p, t, q] for every
+ *                  t + q = k (it stores nmoment^2 copies); pixel
+ *                  (psf_ny/2, psf_nx/2) lands on the peak, the patch is
+ *                  [peak - n/2, peak + n/2) clipped
+ *   scale_kernels  [nscales, psf_ny, psf_nx]: added into every model moment,
+ *                  times gain * mval[moment], on the patch
+ *   scale_extent   as for sdp_hip_clean_plane
+ *   windowstack    [nscales, ny, nx] or NULL
+ *   sensitivity    [ny, nx] or NULL
+ *   hsmmpsf, ihsmmpsf  [nscales, nmoment, nmoment] host doubles: the Hessian
+ *                  of every scale and its inverse
+ *   findpeak       SDP_HIP_MFSCLEAN_FINDPEAK_RASCIL: the search field of
+ *                  scale s is the principal solution's moment 0 (the
+ *                  reference's "RASCIL", "Algorithm1" and anything else);
+ *                  _CASA: its dchisq
+ *   absthresh      max(thresh, fracthresh * max|smresidual[0, 0]|): a cycle
+ *                  whose |mval[0]| is below it is counted and stops, before
+ *                  its update
+ * Per scale the peak is the first maximum of |field| in row-major order,
+ * WITHOUT window or sensitivity; the scales are compared on
+ * max|field * window * sensitivity| with a strict '>' from 0 (the lower
+ * scale wins a tie; nothing above 0 selects pixel (0, 0) of scale 0).
+ * *niter_done is the reference's iteration count, *stop_reason
+ * SDP_HIP_CLEAN_STOP_NITER or _THRESHOLD, scale_counts[nscales] (host) the
+ * cycles that chose each scale.  The call returns after the last cycle.
+ */
+#define SDP_HIP_MFSCLEAN_FINDPEAK_RASCIL 0
+#define SDP_HIP_MFSCLEAN_FINDPEAK_CASA 1
+int sdp_hip_mfsclean_plane(int nscales, int nmoment, int ny, int nx,
+                           int psf_ny, int psf_nx, double *smresidual,
+                           double *m_model, const double *ssmmpsf,
+                           const double *scale_kernels, int scale_extent,
+                           const double *windowstack,
+                           const double *sensitivity, const double *hsmmpsf,
+                           const double *ihsmmpsf, int findpeak, double gain,
+                           double absthresh, int niter, int *niter_done,
+                           int *stop_reason, int *scale_counts, void *stream,
+                           char *errbuf, size_t errbuf_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,8 @@ SDP_HIP_SLOT1 = 256
 
 SDP_HIP_CLEAN_HOGBOM = 0
 SDP_HIP_CLEAN_MSCLEAN = 1
+SDP_HIP_MFSCLEAN_FINDPEAK_RASCIL = 0
+SDP_HIP_MFSCLEAN_FINDPEAK_CASA = 1
 
 c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
@@ -194,6 +196,12 @@ SIGNATURES = {
         c_vp, c_vp, c_int, c_vp,                    # coupling_diag (host), scale_kernels, extent, comps
         c_dbl, c_dbl, c_dbl, c_int,                 # gain, pmax, absthresh, niter
         ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_vp] + _ERR,
+    "sdp_hip_mfsclean_plane": [
+        c_int, c_int, c_int, c_int, c_int, c_int,   # nscales, nmoment, ny, nx, psf_ny, psf_nx
+        c_vp, c_vp, c_vp, c_vp, c_int,              # smresidual, m_model, ssmmpsf, scale_kernels, extent
+        c_vp, c_vp, c_vp, c_vp,                     # windowstack, sensitivity, hsmmpsf, ihsmmpsf (host)
+        c_int, c_dbl, c_dbl, c_int,                 # findpeak, gain, absthresh, niter
+        ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_vp, c_vp] + _ERR,  # done, reason, counts (host)
 }
 
 _lock = threading.Lock()

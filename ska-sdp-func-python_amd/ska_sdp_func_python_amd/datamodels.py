@@ -296,7 +296,8 @@ class WCS:
         self.naxis = naxis
 
     def sub(self, axes):
-        idx = [a - 1 for a in axes]
+        """The WCS of the given axes: 1-based numbers, or "spectral" for the FREQ axis."""
+        idx = [self.wcs.ctype.index("FREQ") if a == "spectral" else a - 1 for a in axes]
         w = WCS(len(idx), [self.wcs.ctype[i] for i in idx], [self.wcs.crpix[i] for i in idx],
                 [self.wcs.cdelt[i] for i in idx], [self.wcs.crval[i] for i in idx],
                 [self.wcs.cunit[i] for i in idx])
@@ -620,6 +621,12 @@ class Image(Dataset):
     @property
     def image_acc(self):
         return _ImageAcc(self)
+
+    @property
+    def frequency(self):
+        """The channel frequencies (Hz), derived from the spectral axis of the WCS."""
+        channels = np.arange(self._vars["pixels"].shape[0])
+        return _Derived(self.attrs["wcs"].sub(["spectral"]).wcs_pix2world(channels, 0)[0])
 
     def copy(self, deep=True, data=None, zero=False):
         """``data`` (xarray's copy(data=...)) becomes the copy's pixels as is."""

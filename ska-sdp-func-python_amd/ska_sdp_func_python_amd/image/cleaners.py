@@ -1,16 +1,19 @@
-"""Image-plane cleaners on 2-D arrays (reference
-src/ska_sdp_func_python/image/cleaners.py): ``hogbom`` (:23-133) and
-``msclean`` (:279-470) with the scale-stack helpers (:473-562).
+"""Image-plane cleaners on 2-D arrays and moment stacks (reference
+src/ska_sdp_func_python/image/cleaners.py): ``hogbom`` (:23-133), ``msclean``
+(:279-470) with the scale-stack helpers (:473-562), and ``msmfsclean``
+(:686-898) with its set-up helpers (:1034-1104).
 
 The minor cycles run on the device in ``kernels.clean_plane``
-(csrc/clean.hip): the full-image argmax and the shifted PSF subtraction of
-every cycle, in fp64 and in the reference's arithmetic order.  numpy input
-gives numpy output, device tensors give device tensors.
+(csrc/clean.hip) and ``kernels.mfsclean_plane`` (csrc/mfsclean.hip): the
+full-image search and the shifted PSF subtraction of every cycle, in fp64 and
+in the reference's arithmetic order.  numpy input gives numpy output, device
+tensors give device tensors.
 
-The msclean set-up (scale stacks, the S + S^2 FFT convolutions, the coupling
-matrix, the window stack) is not the hot path: it is numpy on the host for
-numpy input -- the reference's own operations, so the minor cycles start from
-its bits -- and ``torch.fft`` in fp64 for device input.
+The set-up (scale stacks, the FFT convolutions -- S + S^2 for msclean,
+S T + S^2 (2T - 1) for msmfsclean --, the coupling matrix or Hessians, the
+window stack) is not the hot path: it is numpy on the host for numpy input --
+the reference's own operations, so the minor cycles start from its bits --
+and ``torch.fft`` in fp64 for device input.
 """
 
 import logging
@@ -20,8 +23,10 @@ import torch
 
 from .. import _device, kernels
 
-__all__ = ["hogbom", "msclean", "hogbom_run", "msclean_run", "create_scalestack",
-           "convolve_scalestack", "convolve_convolve_scalestack", "spheroidal_function"]
+__all__ = ["hogbom", "msclean", "msmfsclean", "hogbom_run", "msclean_run", "msmfsclean_run",
+           "create_scalestack", "convolve_scalestack", "convolve_convolve_scalestack",
+           "calculate_scale_moment_residual", "calculate_scale_scale_moment_moment_psf",
+           "calculate_scale_inverse_moment_moment_hessian", "spheroidal_function"]
 
 log = logging.getLogger("func-python-logger")
 
@@ -142,6 +147,149 @@ def msclean(dirty, psf, window, sensitivity, gain, thresh, niter, scales, fracth
     """
     return msclean_run(dirty, psf, window, sensitivity, gain, thresh, niter, scales, fracthresh,
                        prefix)[:2]
+
+
+def msmfsclean_run(dirty, psf, window, sensitivity, gain, thresh, niter, scales, fracthresh,
+                   findpeak="RASCIL", prefix=""):
+    """``msmfsclean`` that also reports what the minor cycle did: returns
+    (m_model, residual, {"niter": cycles, "stop": "niter" | "threshold",
+    "scale_counts": cycles that chose each scale})."""
+    assert 0.0 < gain < 2.0
+    assert niter > 0
+    assert len(scales) > 0
+    on_dev = _device.is_device(dirty)
+    if on_dev:
+        conv = _dev64
+    else:
+        conv = lambda a: numpy.asarray(a, dtype=float)
+    dirty_, psf_ = conv(dirty), conv(psf)
+    window_ = None if window is None else conv(window)
+    pmax = float(psf_.max())
+    assert pmax > 0.0
+    lpsf = psf_ / pmax
+    ldirty = dirty_ / pmax
+    nmoment = ldirty.shape[0]
+    if nmoment > 1:
+        assert psf_.shape[0] == 2 * nmoment
+
+    ns = len(scales)
+    scalestack = create_scalestack([ns, ldirty.shape[1], ldirty.shape[2]], scales, norm=True)
+    pscalestack = create_scalestack([ns, lpsf.shape[1], lpsf.shape[2]], scales, norm=True)
+    # how far the scale kernels reach from the PSF origin: the model update
+    # visits only that part of the patch
+    nz = numpy.nonzero(pscalestack.any(axis=0))
+    extent = int(max(abs(nz[0] - lpsf.shape[1] // 2).max(), abs(nz[1] - lpsf.shape[2] // 2).max(), 1))
+    if on_dev:
+        scalestack, pscalestack = _dev64(scalestack), _dev64(pscalestack)
+    smresidual = calculate_scale_moment_residual(ldirty, scalestack)
+    ssmmpsf = calculate_scale_scale_moment_moment_psf(lpsf, pscalestack)
+    hsmmpsf, ihsmmpsf = calculate_scale_inverse_moment_moment_hessian(ssmmpsf)
+    for s in range(ns):
+        log.debug("mmclean %s: Moment-moment coupling matrix[scale %d] =\n %s", prefix, s, hsmmpsf[s])
+
+    windowstack = None
+    if window_ is not None:
+        smooth = convolve_scalestack(scalestack, window_)
+        windowstack = (smooth > 0.9).to(torch.float64) if on_dev else (smooth > 0.9).astype(float)
+
+    if sensitivity is not None:
+        sensitivity = conv(sensitivity)
+        if sensitivity.ndim == 3:
+            # the reference broadcasts [nmoment, ny, nx] against the 2-D search
+            # field and takes the maximum over the moments too; rounding is
+            # monotone, so max_m |s_m * f| = |max_m |s_m| * f| exactly
+            sensitivity = abs(sensitivity).amax(0) if on_dev else abs(sensitivity).max(0)
+
+    maxabs = float(abs(smresidual[0, 0]).max())
+    absolutethresh = max(thresh, fracthresh * maxabs)
+    log.info("mmclean %s: This minor cycle will stop at %d iterations or peak < %.6f (Jy/beam)",
+             prefix, niter, absolutethresh)
+
+    res = _dev64(smresidual)
+    m_model = torch.zeros_like(res[0])
+    done, stop, counts = kernels.mfsclean_plane(
+        res, m_model, _dev64(ssmmpsf), _dev64(pscalestack), hsmmpsf, ihsmmpsf, gain, absolutethresh,
+        niter, findpeak=findpeak,
+        windowstack=None if windowstack is None else _dev64(windowstack),
+        sensitivity=None if sensitivity is None else _dev64(sensitivity), scale_extent=extent)
+    log.info("mmclean %s: End of minor cycles: %d iterations (%s), scale counts %s", prefix, done,
+             stop, counts)
+    return (_device.like_input(m_model, dirty), _device.like_input(pmax * res[0], dirty),
+            {"niter": done, "stop": stop, "scale_counts": counts})
+
+
+def msmfsclean(dirty, psf, window, sensitivity, gain, thresh, niter, scales, fracthresh,
+               findpeak="RASCIL", prefix=""):
+    """Multi-scale multi-frequency CLEAN (Rau & Cornwell 2011, Algorithm 1;
+    the image-plane part) on frequency moments.
+
+    :param dirty: dirty moment images [nmoment, ny, nx], nmoment <= 4
+    :param psf: PSF moment images [2 * nmoment, py, px] ([1 or more, py, px]
+                for nmoment 1, of which moment 0 is used), any size
+    :param window: clean window [ny, nx] or None.  Each scale's window is the
+                window smoothed by that scale, where it exceeds 0.9.  As in
+                the reference it (and the sensitivity) only weigh the choice
+                between scales: the pixel of each scale is the peak of the
+                unweighted search image
+    :param sensitivity: inverse noise image [ny, nx] or [nmoment, ny, nx], or None
+    :param gain: loop gain
+    :param thresh: stop once |moment 0 of the peak's principal solution| <
+                max(thresh, fracthresh * max|dirty moment 0 smoothed by scale 0|)
+    :param niter: maximum number of components
+    :param scales: scale sizes in pixels (at most 16)
+    :param fracthresh: fractional threshold
+    :param findpeak: "CASA" searches the chi-squared decrease, "RASCIL",
+                "Algorithm1" and anything else moment 0 of the principal solution
+    :return: model moment images, residual moment images
+    """
+    return msmfsclean_run(dirty, psf, window, sensitivity, gain, thresh, niter, scales, fracthresh,
+                          findpeak, prefix)[:2]
+
+
+def _stack(planes, axis=0):
+    if isinstance(planes[0], torch.Tensor):
+        return torch.stack(planes, dim=axis)
+    return numpy.stack(planes, axis=axis)
+
+
+def calculate_scale_moment_residual(residual, scalestack):
+    """Every moment of ``residual`` [nmoment, ny, nx] smoothed by every scale:
+    [nscales, nmoment, ny, nx] (Algorithm 1, lines 12 - 17)."""
+    return _stack([convolve_scalestack(scalestack, residual[t]) for t in range(residual.shape[0])],
+                  axis=1)
+
+
+def calculate_scale_scale_moment_moment_psf(psf, scalestack):
+    """The PSF moments smoothed by every pair of scales (Algorithm 1, lines 3 - 5),
+    in compact form: [nscales, nscales, 2 * nmoment - 1, py, px] with nmoment =
+    max(psf.shape[0] // 2, 1).  Plane k is the reference's
+    ``ssmmpsf[s, p, t, q]`` for every t + q = k; the reference stores those
+    nmoment^2 copies of the 2 * nmoment - 1 distinct arrays."""
+    nmoment = max(psf.shape[0] // 2, 1)
+    return _stack([convolve_convolve_scalestack(scalestack, psf[k]) for k in range(2 * nmoment - 1)],
+                  axis=2)
+
+
+def calculate_scale_inverse_moment_moment_hessian(scale_scale_moment_moment_psf):
+    """Hessian [nscales, nmoment, nmoment] of every scale, read at the PSF
+    origin (py // 2, px // 2) of ``ssmmpsf[s, s]``, and its inverse
+    (Algorithm 1, lines 7 - 9); host numpy, ``numpy.linalg.inv``.  Takes the
+    compact form of ``calculate_scale_scale_moment_moment_psf`` or the
+    reference's [nscales, nscales, nmoment, nmoment, py, px]."""
+    ssmm = scale_scale_moment_moment_psf
+    ns = ssmm.shape[0]
+    cy, cx = ssmm.shape[-2] // 2, ssmm.shape[-1] // 2
+    centre = ssmm[..., cy, cx]
+    centre = centre.cpu().numpy() if isinstance(centre, torch.Tensor) else numpy.asarray(centre)
+    nmoment = centre.shape[2] if centre.ndim == 4 else (centre.shape[2] + 1) // 2
+    hessian = numpy.zeros([ns, nmoment, nmoment])
+    inverse = numpy.zeros([ns, nmoment, nmoment])
+    for s in range(ns):
+        for t in range(nmoment):
+            for q in range(nmoment):
+                hessian[s, t, q] = centre[s, s, t, q] if centre.ndim == 4 else centre[s, s, t + q]
+        inverse[s] = numpy.linalg.inv(hessian[s])
+    return hessian, inverse
 
 
 # Schwab (1984, Indirect Imaging) rational approximation of the prolate

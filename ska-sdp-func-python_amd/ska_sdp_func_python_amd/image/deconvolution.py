@@ -1,15 +1,18 @@
 """Deconvolution and restore of image cubes (reference
 src/ska_sdp_func_python/image/deconvolution.py): ``deconvolve_cube`` /
-``deconvolve_list`` (:50-160, :1047-1116) over the Hogbom and multi-scale
-cleaners, and ``restore_cube`` / ``restore_list`` / ``fit_psf`` (:949-1189).
+``deconvolve_list`` (:50-160, :1047-1116) over the Hogbom, multi-scale and
+multi-scale multi-frequency cleaners (``mmclean_kernel_list``, :645-824), and
+``restore_cube`` / ``restore_list`` / ``fit_psf`` (:949-1189).
 
-Planes are cleaned one channel and polarisation at a time by
-``image.cleaners`` (the minor cycles are HIP, csrc/clean.hip); the restore is
-a circular convolution with ``torch.fft`` on the device.  Pixels may be numpy
-arrays or device tensors; outputs follow the dirty (model) image.
+Hogbom and msclean clean one channel and polarisation at a time; the
+``msmfsclean`` family ("msmfsclean", "mfsmsclean", "mmclean") cleans the
+frequency moments of all channels of a polarisation together
+(``image.taylor_terms``).  The minor cycles are HIP (``image.cleaners``,
+csrc/clean.hip and csrc/mfsclean.hip); the restore is a circular convolution
+with ``torch.fft`` on the device.  Pixels may be numpy arrays or device
+tensors; outputs follow the dirty (model) image.
 
-The ``msmfsclean`` family and ``hogbom-complex`` are not provided and raise
-``ValueError``.
+``hogbom-complex`` is not provided and raises ``ValueError``.
 """
 
 import logging
@@ -20,16 +23,19 @@ import torch
 
 from .. import _device
 from ..datamodels import Image
-from .cleaners import hogbom, msclean
+from .cleaners import hogbom, msclean, msmfsclean
 from .operations import convert_clean_beam_to_degrees, convert_clean_beam_to_pixels
+from .taylor_terms import (calculate_image_list_frequency_moments,
+                           calculate_image_list_from_frequency_taylor_terms)
 
 __all__ = ["deconvolve_cube", "deconvolve_list", "hogbom_kernel_list", "msclean_kernel_list",
-           "find_window_list", "bound_psf_list", "check_psf_peak", "common_arguments",
+           "mmclean_kernel_list", "find_window_list", "bound_psf_list", "check_psf_peak", "common_arguments",
            "restore_cube", "restore_list", "fit_psf"]
 
 log = logging.getLogger("func-python-logger")
 
-_UNSUPPORTED = ("msmfsclean", "mfsmsclean", "mmclean", "hogbom-complex")
+_MMCLEAN = ("msmfsclean", "mfsmsclean", "mmclean")
+_UNSUPPORTED = ("hogbom-complex",)
 
 
 def _pixels(im):
@@ -82,8 +88,10 @@ def deconvolve_list(dirty_list, psf_list, sensitivity_list=None, prefix="", **kw
     :param window_edge: edge width of "no_edge" (16)
     :param mask: window Image, overrides ``window_shape``
     :param psf_support: half width of the PSF box used for the subtraction
-    :param algorithm: "msclean" (default) or "hogbom"
-    :param gain: loop gain (0.1)
+    :param algorithm: "msclean" (default), "hogbom", or "msmfsclean" /
+        "mfsmsclean" / "mmclean" (see ``mmclean_kernel_list`` for ``nmoment``
+        and ``findpeak``)
+    :param gain: loop gain (0.1; 0.7 for the msmfsclean family)
     :param niter: minor cycles (100)
     :param threshold: clean threshold (0.0)
     :param fractional_threshold: fractional threshold (0.01)
@@ -96,7 +104,7 @@ def deconvolve_list(dirty_list, psf_list, sensitivity_list=None, prefix="", **kw
     algorithm = kwargs.get("algorithm", "msclean")
     if algorithm in _UNSUPPORTED:
         raise ValueError(f"deconvolve_cube {prefix}: algorithm {algorithm} is not provided")
-    if algorithm not in ("msclean", "hogbom"):
+    if algorithm not in ("msclean", "hogbom") + _MMCLEAN:
         raise ValueError(f"deconvolve_cube {prefix}: Unknown algorithm {algorithm}")
 
     # window_edge and mask are handed on to find_window_list, which documents
@@ -110,6 +118,9 @@ def deconvolve_list(dirty_list, psf_list, sensitivity_list=None, prefix="", **kw
 
     if algorithm == "msclean":
         return msclean_kernel_list(dirty_list, prefix, psf_list, window_list, sensitivity_list,
+                                   **kwargs)
+    if algorithm in _MMCLEAN:
+        return mmclean_kernel_list(dirty_list, prefix, psf_list, window_list, sensitivity_list,
                                    **kwargs)
     return hogbom_kernel_list(dirty_list, prefix, psf_list, window_list, **kwargs)
 
@@ -247,6 +258,77 @@ def msclean_kernel_list(dirty_list, prefix, psf_list, window_list, sensitivity_l
         lambda d, p, channel, pol: msclean(d, p, _plane(window_list, channel, pol),
                                            _plane(sensitivity_list, channel, pol), gain, thresh,
                                            niter, scales, fracthresh, prefix))
+
+
+def mmclean_kernel_list(dirty_list, prefix, psf_list, window_list=None, sensitivity_list=None,
+                        **kwargs):
+    """Multi-scale multi-frequency clean ("msmfsclean", "mfsmsclean",
+    "mmclean"; Rau & Cornwell 2011) of every polarisation: the channels are
+    turned into ``nmoment`` frequency moments (Taylor terms), the moments are
+    cleaned together by ``cleaners.msmfsclean`` and the cleaned moments are
+    turned back into channel images.
+
+    :param nmoment: number of frequency moments (3); ``nchan > 2 * (nmoment - 1)``
+        is required, since the PSF needs 2 * nmoment moments (1 for nmoment 1)
+    :param gain: loop gain (0.7, unlike the other cleaners)
+    :param findpeak: "RASCIL" (default), "Algorithm1" or "CASA"
+    :param niter, threshold, fractional_threshold, scales: see ``deconvolve_list``
+    :return: component image list, residual image list
+
+    As in the reference, every polarisation is cleaned with the PSF moments of
+    polarisation 0 and with the window of channel moment 0; the window moment
+    and the sensitivity moments are divided by nchan, the dirty and PSF
+    moments by the peak of the PSF moments; all polarisations are skipped only
+    if PSF moment 0 of polarisation 0 has maximum 0.
+    """
+    findpeak = kwargs.get("findpeak", "RASCIL")
+    nmoment = kwargs.get("nmoment", 3)
+    if not nmoment >= 1:
+        raise ValueError("Number of frequency moments must be greater than or equal to one")
+    fracthresh, gain, niter, thresh, scales = common_arguments(**kwargs)
+    gain = kwargs.get("gain", 0.7)
+    if not 0.0 < gain < 2.0:
+        raise ValueError("Loop gain must be between 0 and 2")
+    nchan = len(dirty_list)
+    if not nchan > 2 * (nmoment - 1):
+        raise ValueError(f"deconvolve_cube {prefix}: algorithm {kwargs.get('algorithm', 'mmclean')} "
+                         f"requires nchan > 2 * (nmoment - 1) ({nchan} > {2 * (nmoment - 1)})")
+
+    moment_image = calculate_image_list_frequency_moments(dirty_list, nmoment=nmoment)
+    dirty_taylor = _pixels(moment_image)
+    sensitivity_taylor = window_taylor = None
+    if sensitivity_list is not None:
+        sensitivity_taylor = _pixels(calculate_image_list_frequency_moments(
+            sensitivity_list, nmoment=nmoment)) / nchan
+    if window_list is not None:
+        window_taylor = _pixels(calculate_image_list_frequency_moments(
+            window_list, nmoment=nmoment)) / nchan
+    psf_taylor = _pixels(calculate_image_list_frequency_moments(
+        psf_list, nmoment=2 * nmoment if nmoment > 1 else 1))
+    psf_peak = float(psf_taylor.max())
+    dirty_taylor = dirty_taylor / psf_peak
+    psf_taylor = psf_taylor / psf_peak
+    log.info("mmclean_kernel_list %s: Shape of Dirty moments image %s, of PSF moments image %s",
+             prefix, tuple(dirty_taylor.shape), tuple(psf_taylor.shape))
+
+    comp_array = _zeros_like(dirty_taylor)
+    residual_array = _zeros_like(dirty_taylor)
+    for pol in range(dirty_taylor.shape[1]):
+        # always the moment 0, polarisation 0 PSF
+        if float(psf_taylor[0, 0].max()):
+            log.info("mmclean_kernel_list %s: Processing pol %d", prefix, pol)
+            comp_array[:, pol], residual_array[:, pol] = msmfsclean(
+                dirty_taylor[:, pol], psf_taylor[:, 0],
+                None if window_taylor is None else window_taylor[0, pol],
+                None if sensitivity_taylor is None else sensitivity_taylor[:, pol],
+                gain, thresh, niter, scales, fracthresh, findpeak, prefix)
+        else:
+            log.info("mmclean_kernel_list %s: Skipping pol %d", prefix, pol)
+
+    comp_taylor = _image_like(comp_array, moment_image)
+    residual_taylor = _image_like(residual_array, moment_image)
+    return (calculate_image_list_from_frequency_taylor_terms(dirty_list, comp_taylor),
+            calculate_image_list_from_frequency_taylor_terms(dirty_list, residual_taylor))
 
 
 def deconvolve_cube(dirty, psf, sensitivity=None, prefix="", **kwargs):

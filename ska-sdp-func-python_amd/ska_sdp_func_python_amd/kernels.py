@@ -951,3 +951,48 @@ def clean_plane(algorithm, res, psf, comps, gain, pmax, absthresh, niter, window
               _ptr(scale_kernels if ms else None), int(scale_extent), _ptr(comps), float(gain), float(pmax), float(absthresh), int(niter),
               ctypes.byref(done), ctypes.byref(reason), _stream(res.device))
     return done.value, CLEAN_STOP[reason.value]
+
+
+# ---- msmfsclean minor cycles (sdp_hip_mfsclean_plane) ----------------------------
+def mfsclean_plane(smresidual, m_model, ssmmpsf, scale_kernels, hsmmpsf, ihsmmpsf, gain, absthresh,
+                   niter, findpeak="RASCIL", windowstack=None, sensitivity=None, scale_extent=0):
+    """Up to ``niter`` multi-scale multi-frequency CLEAN minor cycles of one
+    polarisation, in place on device f64: ``smresidual`` [S, T, ny, nx],
+    ``m_model`` [T, ny, nx], ``ssmmpsf`` [S, S, 2T - 1, py, px] (plane k holds
+    the moment pairs t + q = k), ``scale_kernels`` [S, py, px], which
+    ``scale_extent`` > 0 declares zero further than that many pixels from
+    (py // 2, px // 2); optional ``windowstack`` [S, ny, nx] and
+    ``sensitivity`` [ny, nx]; ``hsmmpsf`` and ``ihsmmpsf`` [S, T, T] on the
+    host.  ``findpeak`` "CASA" searches dchisq, anything else the principal
+    solution's moment 0.  S <= 16, T <= 4.
+    Returns (cycles run, "niter" | "threshold", cycles per scale)."""
+    _on_gpu(smresidual, "smresidual")
+    if smresidual.dim() != 4 or ssmmpsf.dim() != 5:
+        raise ValueError("smresidual must be [S, T, ny, nx] and ssmmpsf [S, S, 2T - 1, py, px]")
+    ns, nt, ny, nx = smresidual.shape
+    pny, pnx = ssmmpsf.shape[3:]
+    _f64_plane(smresidual, "smresidual", (ns, nt, ny, nx))
+    _f64_plane(m_model, "m_model", (nt, ny, nx))
+    _f64_plane(ssmmpsf, "ssmmpsf", (ns, ns, 2 * nt - 1, pny, pnx))
+    _f64_plane(scale_kernels, "scale_kernels", (ns, pny, pnx))
+    if windowstack is not None:
+        _f64_plane(windowstack, "windowstack", (ns, ny, nx))
+    if sensitivity is not None:
+        _f64_plane(sensitivity, "sensitivity", (ny, nx))
+    hess = []
+    for name, h in (("hsmmpsf", hsmmpsf), ("ihsmmpsf", ihsmmpsf)):
+        flat = [float(v) for scale in h for row in scale for v in row]
+        if len(h) != ns or len(flat) != ns * nt * nt:
+            raise ValueError(f"{name} must be a host array of shape {(ns, nt, nt)}")
+        hess.append((ctypes.c_double * len(flat))(*flat))
+    casa = findpeak == "CASA"
+    done, reason = ctypes.c_int(0), ctypes.c_int(0)
+    counts = (ctypes.c_int * ns)()
+    _lib.call("sdp_hip_mfsclean_plane", ns, nt, ny, nx, pny, pnx, _ptr(smresidual), _ptr(m_model),
+              _ptr(ssmmpsf), _ptr(scale_kernels), int(scale_extent), _ptr(windowstack),
+              _ptr(sensitivity), ctypes.cast(hess[0], ctypes.c_void_p),
+              ctypes.cast(hess[1], ctypes.c_void_p),
+              _lib.SDP_HIP_MFSCLEAN_FINDPEAK_CASA if casa else _lib.SDP_HIP_MFSCLEAN_FINDPEAK_RASCIL,
+              float(gain), float(absthresh), int(niter), ctypes.byref(done), ctypes.byref(reason),
+              ctypes.cast(counts, ctypes.c_void_p), _stream(smresidual.device))
+    return done.value, CLEAN_STOP[reason.value], list(counts)
