@@ -397,6 +397,48 @@ int sdp_hip_dft_point_metres(int ncomp, const double *direction_cosines,
                              void *stream, char *errbuf, size_t errbuf_len);
 
 /*
+ * sdp_hip_idft_point_v00 -- the adjoint of sdp_hip_dft_point_v00: the two
+ * sums of idft_visibility_skycomponent (reference
+ * src/ska_sdp_func_python/imaging/dft.py:340-387; flux :365-370, weight
+ * :371, phasor visibility/base.py:27-45) for all components in one call.
+ * Caller-allocated outputs, replaced (not accumulated), all arrays
+ * C-contiguous:
+ *   direction_cosines [ncomp, 3] f64 (l, m, n-1)
+ *   uvw_lambda        [ntimes*nbaselines, nchan, 3] f64 wavelengths
+ *   vis               [ntimes*nbaselines, nchan, npol] c64 or c128
+ *   weight            [ntimes*nbaselines, nchan, npol] f64
+ *   flags             [ntimes*nbaselines, nchan, npol] 0/1 integers of
+ *                     flag_bytes (1, 4 or 8) bytes, or NULL (none flagged)
+ *   flux_sum          [ncomp, nchan, npol] c128
+ *   sumwt             [nchan, npol] f64, or NULL (not wanted)
+ * flux_sum = sum_row weight (1 - flag) vis exp(+2 pi i (u l + v m + w (n-1)))
+ * sumwt    = sum_row weight (1 - flag)
+ * Both are UNNORMALISED: the reference's flux is flux_sum / sumwt where
+ * sumwt > 0 and 0 elsewhere (:373-374), left to the caller so that row shards
+ * can be summed first.  complex128 vis: fp64 sincos, products and sums;
+ * complex64 vis: fp32 sincos and products, fp32 partial sums of at most 32
+ * terms added into fp64.  No atomics: the same inputs give the same bits.
+ * nrow == 0 writes zeros; ncomp == 0 writes only sumwt; npol must be 1, 2 or
+ * 4 (SDP_HIP_ERR_INVALID_ARG otherwise).
+ */
+int sdp_hip_idft_point_v00(int ncomp, const double *direction_cosines, int npol,
+                           int64_t nrow, int nchan, const double *uvw_lambda,
+                           const void *vis, int vis_dtype, const double *weight,
+                           const void *flags, int flag_bytes, void *flux_sum,
+                           double *sumwt, void *stream, char *errbuf,
+                           size_t errbuf_len);
+
+/* Same sums with uvw in metres [nrow, 3] + freq [nchan]: the lambda scaling
+ * (reference visibility/base.py:54-56) is fused into the kernel so the
+ * [nrow, nchan, 3] uvw_lambda array is never materialised. */
+int sdp_hip_idft_point_metres(int ncomp, const double *direction_cosines, int npol,
+                              int64_t nrow, int nchan, const double *uvw,
+                              const double *freq, const void *vis, int vis_dtype,
+                              const double *weight, const void *flags,
+                              int flag_bytes, void *flux_sum, double *sumwt,
+                              void *stream, char *errbuf, size_t errbuf_len);
+
+/*
  * Convolution-function (AW-projection) gridder/degridder, replacing the
  * Python triple loops of grid_visibility_to_griddata /
  * degrid_visibility_from_griddata (reference

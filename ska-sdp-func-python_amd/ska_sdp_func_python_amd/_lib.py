@@ -163,6 +163,14 @@ SIGNATURES = {
     "sdp_hip_dft_point_metres": [
         c_int, c_vp, c_vp, c_int, c_int, c_i64, c_int, c_vp, c_vp, c_vp, c_int,
         c_vp] + _ERR,
+    "sdp_hip_idft_point_v00": [
+        c_int, c_vp, c_int, c_i64, c_int, c_vp,   # ncomp, dc, npol, nrow, nchan, uvw_lambda
+        c_vp, c_int, c_vp, c_vp, c_int,           # vis, dtype, weight, flags, flag_bytes
+        c_vp, c_vp, c_vp] + _ERR,                 # flux_sum, sumwt, stream
+    "sdp_hip_idft_point_metres": [
+        c_int, c_vp, c_int, c_i64, c_int, c_vp, c_vp,  # ..., uvw (metres), freq
+        c_vp, c_int, c_vp, c_vp, c_int,
+        c_vp, c_vp, c_vp] + _ERR,
     "sdp_hip_grid_cf": [
         c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
         c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_int,

@@ -1,9 +1,10 @@
-"""Sky-component DFT predict on MI355X.
+"""Sky-component DFT predict and its inverse on MI355X.
 
 Mirrors reference ``src/ska_sdp_func_python/imaging/dft.py``:
 ``dft_skycomponent_visibility`` (:32-56, replaces ``vis["vis"]``),
 ``extract_direction_and_flux`` (:59-118: pol-frame conversion, cubic
-frequency interpolation, lmn with n-1) and ``dft_kernel`` (:121-182).
+frequency interpolation, lmn with n-1), ``dft_kernel`` (:121-182) and
+``idft_visibility_skycomponent`` (:340-387, sdp_hip_idft_point_metres).
 
 Every ``dft_compute_kernel`` the reference knows ("cpu_looped",
 "gpu_cupy_raw", "proc_func") and "hip" run the same HIP kernel
@@ -44,6 +45,55 @@ def dft_skycomponent_visibility(vis, sc, dft_compute_kernel=None):
                             else torch.complex128)
     vis["vis"].data = _device.like_input(out.reshape(nt, nb, nchan, npol), ref)
     return vis
+
+
+def idft_visibility_skycomponent(vis, sc):
+    """Component fluxes read back out of ``vis`` (reference dft.py:340-387):
+    per component the weighted, flag-masked visibilities times the conjugate
+    phasor summed over times and baselines, divided by the summed weight
+    (0 where that is not positive), in the component's polarisation frame.
+    Returns (list of new SkyComponents, list of [nchan, npol] weights).
+    All components go through one sdp_hip_idft_point_metres call."""
+    if sc is None:
+        return sc
+    if not isinstance(sc, collections.abc.Iterable):
+        sc = [sc]
+    sc = list(sc)
+    newsc = [comp.copy() for comp in sc]
+    if not newsc:
+        return newsc, []
+    direction_cosines = []
+    for comp in sc:
+        l, m, _ = skycoord_to_lmn(comp.direction, vis.phasecentre)
+        direction_cosines.append(np.array([l, m, np.sqrt(1 - l ** 2 - m ** 2) - 1.0]))
+    dev = _device.device()
+    ref = vis["vis"].data
+    nt, nb, nchan, npol = ref.shape
+    v = _device.to_dev(ref, None, dev)
+    if v.dtype not in (torch.complex64, torch.complex128):
+        v = v.to(torch.complex128)
+    flags = _device.to_dev(vis["flags"].data, None, dev)
+    if flags.dtype not in kernels._FLAG_DT:
+        flags = flags.to(torch.int64)
+    uvw = _device.to_dev(vis.uvw.data, torch.float64, dev).reshape(nt * nb, 3)
+    freq = _device.to_dev(np.asarray(vis.frequency.data, float), torch.float64, dev)
+    flux_sum, sumwt = kernels.idft_point(
+        _device.to_dev(np.array(direction_cosines), torch.float64, dev),
+        v.reshape(nt * nb, nchan, npol),
+        _device.to_dev(vis["weight"].data, torch.float64, dev).reshape(nt * nb, nchan, npol),
+        uvw, freq=freq, flags=flags.reshape(nt * nb, nchan, npol))
+    good = sumwt > 0.0
+    flux = torch.where(good, flux_sum / torch.where(good, sumwt, torch.ones_like(sumwt)),
+                       torch.zeros_like(flux_sum))
+    vpf = vis.visibility_acc.polarisation_frame
+    weights_list = []
+    for i, newcomp in enumerate(newsc):
+        f = flux[i]
+        if newcomp.polarisation_frame != vpf:
+            f = convert_pol_frame(f, vpf, newcomp.polarisation_frame)
+        newcomp.flux = _device.like_input(f, ref)
+        weights_list.append(_device.like_input(sumwt.clone(), ref))
+    return newsc, weights_list
 
 
 def extract_direction_and_flux(sc, vis):

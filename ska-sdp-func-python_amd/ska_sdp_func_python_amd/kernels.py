@@ -599,6 +599,63 @@ def dft_point(direction_cosines, fluxes, uvw, freq=None, out=None, vis_dtype=tor
     return out
 
 
+def idft_point(direction_cosines, vis, weight, uvw, freq=None, flags=None, out=None):
+    """Inverse sky-component DFT on device: the adjoint of ``dft_point``.
+
+    direction_cosines [ncomp,3] f64; vis [nrow, nchan, npol] c64 or c128;
+    weight f64 and flags (integers, 0/1, or None) shaped like vis.  With
+    ``freq`` given, ``uvw`` is [nrow,3] metres (lambda scaling fused);
+    otherwise ``uvw`` is uvw_lambda [nrow, nchan, 3].
+    Returns (flux_sum [ncomp, nchan, npol] c128, sumwt [nchan, npol] f64):
+    sum_row w (1-flag) vis exp(+2 pi i ...) and sum_row w (1-flag), both
+    unnormalised (the reference's flux is flux_sum / sumwt where sumwt > 0).
+    ``out`` = (flux_sum, sumwt) writes into caller-allocated tensors.
+    """
+    dc = _on_gpu(direction_cosines, "direction_cosines").to(torch.float64).contiguous()
+    if dc.dim() != 2 or dc.shape[1] != 3:
+        raise ValueError("direction_cosines [ncomp,3] required")
+    vis = _on_gpu(vis, "vis")
+    if vis.dtype not in (torch.complex64, torch.complex128) or vis.dim() != 3:
+        raise ValueError("vis must be complex64 or complex128 [nrow, nchan, npol]")
+    vis = vis.contiguous()
+    nrow, nchan, npol = vis.shape
+    weight = _on_gpu(weight, "weight").to(torch.float64).contiguous()
+    if tuple(weight.shape) != (nrow, nchan, npol):
+        raise ValueError("weight must be shaped like vis")
+    fb = 0
+    if flags is not None:
+        flags = _on_gpu(flags, "flags").contiguous()
+        if tuple(flags.shape) != (nrow, nchan, npol) or flags.dtype not in _FLAG_DT:
+            raise ValueError("flags must be an integer tensor shaped like vis")
+        fb = _FLAG_DT[flags.dtype]
+    uvw = _on_gpu(uvw, "uvw").to(torch.float64).contiguous()
+    if freq is not None:
+        freq = _on_gpu(freq, "freq").to(torch.float64).contiguous()
+        if tuple(uvw.shape) != (nrow, 3) or tuple(freq.shape) != (nchan,):
+            raise ValueError("uvw [nrow,3] metres and freq [nchan] must match vis")
+    elif tuple(uvw.shape) != (nrow, nchan, 3):
+        raise ValueError("uvw_lambda [nrow, nchan, 3] must match vis")
+    ncomp = dc.shape[0]
+    if out is None:
+        out = (_alloc((ncomp, nchan, npol), torch.complex128, vis.device),
+               _alloc((nchan, npol), torch.float64, vis.device))
+    flux_sum, sumwt = out
+    if (not flux_sum.is_contiguous() or tuple(flux_sum.shape) != (ncomp, nchan, npol)
+            or flux_sum.dtype != torch.complex128 or not sumwt.is_contiguous()
+            or tuple(sumwt.shape) != (nchan, npol) or sumwt.dtype != torch.float64):
+        raise ValueError("out must be contiguous (flux_sum [ncomp, nchan, npol] complex128, "
+                         "sumwt [nchan, npol] float64)")
+    if freq is not None:
+        _lib.call("sdp_hip_idft_point_metres", ncomp, _ptr(dc), npol, nrow, nchan, _ptr(uvw),
+                  _ptr(freq), _ptr(vis), _DT_CODE[vis.dtype], _ptr(weight), _ptr(flags), fb,
+                  _ptr(flux_sum), _ptr(sumwt), _stream(vis.device))
+    else:
+        _lib.call("sdp_hip_idft_point_v00", ncomp, _ptr(dc), npol, nrow, nchan, _ptr(uvw),
+                  _ptr(vis), _DT_CODE[vis.dtype], _ptr(weight), _ptr(flags), fb,
+                  _ptr(flux_sum), _ptr(sumwt), _stream(vis.device))
+    return flux_sum, sumwt
+
+
 def canonical_baselines(ant1, ant2, nants):
     """Canonical (a1 < a2) CSR order of a baseline list.
 

@@ -635,6 +635,27 @@ def dft_sharded(direction_cosines, fluxes, uvw, freq=None, group=None, src=0, df
     return dft_fn(direction_cosines, fluxes, uvw, freq=freq)
 
 
+def idft_sharded(direction_cosines, vis, weight, uvw, freq=None, flags=None, group=None, src=0,
+                 idft_fn=None):
+    """Row-sharded inverse sky-component DFT, the counterpart of
+    ``dft_sharded`` (reference imaging/dft.py:340-387).  The component
+    directions are broadcast from rank ``src``; each rank sums its own rows
+    ``vis`` / ``weight`` / ``uvw`` / ``flags``, then the unnormalised
+    ``flux_sum`` [ncomp, nchan, npol] and ``sumwt`` [nchan, npol] are summed
+    across ranks (two all-reduces), so every rank returns the global sums and
+    the division flux_sum / sumwt is the same everywhere."""
+    if idft_fn is None:
+        from . import kernels
+        idft_fn = kernels.idft_point
+    if _dist_on():
+        dist.broadcast(direction_cosines, src=src, group=group)
+    flux_sum, sumwt = idft_fn(direction_cosines, vis, weight, uvw, freq=freq, flags=flags)
+    if _dist_on():
+        all_reduce_sum(flux_sum, group)
+        all_reduce_sum(sumwt, group)
+    return flux_sum, sumwt
+
+
 def normalise_gains_global(gain, normalise_gains, group=None):
     """The reference's gain normalisation over the WHOLE table
     (calibration/solvers.py:135-143) when the gain rows are sharded:
