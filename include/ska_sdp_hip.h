@@ -699,6 +699,82 @@ int sdp_hip_mfsclean_plane(int nscales, int nmoment, int ny, int nx,
                            int *stop_reason, int *scale_counts, void *stream,
                            char *errbuf, size_t errbuf_len);
 
+/*
+ * Visibility operations (reference src/ska_sdp_func_python/visibility/
+ * operations.py).  Arrays are the Visibility's [ntimes, nbl, nchan, npol] in
+ * C order with nrows = ntimes * nbl: vis c64 or c128 (vis_dtype), weight and
+ * imaging_weight f64, flags integers of flag_bytes (1, 4, 8) or NULL;
+ * npol 1, 2 or 4.  Arithmetic is fp64 in numpy's order of operations; a c64
+ * result is rounded once on output.
+ *
+ * sdp_hip_vis_average_channels: integrate_visibility_by_channel (:192-235,
+ * variant 0, group == nchan) and average_visibility_by_channel (:238-306,
+ * variant 1, every group of `group` channels in one call; group divides
+ * nchan).  Outputs [nrows, nchan / group, npol]:
+ *   weight_out         = sum of weight (1 - flag) over the group
+ *   imaging_weight_out = sum of imaging_weight (1 - flag)
+ *   flags_out          = 1 where the group's flag count reaches the TOTAL
+ *                        nchan (both reference functions compare with nchan),
+ *                        else 0; integers of flags_out_bytes
+ *   vis_out            = sum of vis (weight (1 - flag)) [variant 0] or of
+ *                        (vis (1 - flag)) weight [variant 1], divided by
+ *                        d = weight_out (1 - flags_out) where d > 0 (numpy's
+ *                        complex / real division)
+ * The sums add the channels in numpy.sum(axis=-2)'s order: one by one for
+ * npol 2 and 4, numpy's pairwise order for npol 1; with c128 input the result
+ * is numpy's bit for bit.
+ */
+int sdp_hip_vis_average_channels(int64_t nrows, int nchan, int npol, int group,
+                                 int variant, const void *vis, int vis_dtype,
+                                 const double *weight,
+                                 const double *imaging_weight,
+                                 const void *flags, int flag_bytes,
+                                 void *vis_out, double *weight_out,
+                                 double *imaging_weight_out, void *flags_out,
+                                 int flags_out_bytes, void *stream,
+                                 char *errbuf, size_t errbuf_len);
+/*
+ * sdp_hip_vis_to_stokes over nsamples = ntimes * nbl * nchan samples.
+ * SDP_HIP_STOKES_IQUV: convert_visibility_to_stokes (:309-333), in place,
+ * npol 4: vis <- M vis with matrix (HOST, 16 complex as 32 doubles, row =
+ * output pol) and every pol's flag <- flag[0] | flag[3]; the other pointers
+ * are unused.  SDP_HIP_STOKES_I: convert_visibility_to_stokesI (:336-420),
+ * npol 2 or 4, into [nsamples] outputs, with first = pol 0, last = pol
+ * npol - 1 and fv, fw the flagged values:
+ *   vis_out = 0.5 (fv[first] + fv[last]),  weight_out = fw[first] + fw[last]
+ *   (imaging_weight_out likewise),  flags_out = flag[first] | flag[last]
+ */
+#define SDP_HIP_STOKES_IQUV 0
+#define SDP_HIP_STOKES_I 1
+int sdp_hip_vis_to_stokes(int64_t nsamples, int npol, int mode, void *vis,
+                          int vis_dtype, const double *weight,
+                          const double *imaging_weight, void *flags,
+                          int flag_bytes, const double *matrix, void *vis_out,
+                          double *weight_out, double *imaging_weight_out,
+                          void *flags_out, int flags_out_bytes, void *stream,
+                          char *errbuf, size_t errbuf_len);
+/*
+ * sdp_hip_vis_remove_continuum: remove_continuum_visibility (:108-142), in
+ * place.  For each spectrum (row, pol) a polynomial of `degree` (0 to 5) in
+ * x[nchan] (device f64, the reference's scaled frequency) is fitted to vis
+ * with weights weight (1 - flag), 0 where mask[nchan] (device uint8, or NULL)
+ * is non-zero, and subtracted at every channel.  The fit uses the orthogonal
+ * polynomials of the spectrum's own weights (no normal equations).  With
+ * n_live the number of channels of non-zero fit weight: a spectrum with
+ * n_live == 0 is left unchanged; one with 1 <= n_live <= degree is left
+ * unchanged and its index row * npol + pol is appended (in no particular
+ * order) to rank_list[rank_capacity] (device int32); *rank_count (device
+ * int32) receives their number, which may exceed rank_capacity.
+ */
+int sdp_hip_vis_remove_continuum(int64_t nrows, int nchan, int npol, void *vis,
+                                 int vis_dtype, const double *weight,
+                                 const void *flags, int flag_bytes,
+                                 const double *x, const uint8_t *mask,
+                                 int degree, int32_t *rank_list,
+                                 int rank_capacity, int32_t *rank_count,
+                                 void *stream, char *errbuf,
+                                 size_t errbuf_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,8 @@ SDP_HIP_CLEAN_HOGBOM = 0
 SDP_HIP_CLEAN_MSCLEAN = 1
 SDP_HIP_MFSCLEAN_FINDPEAK_RASCIL = 0
 SDP_HIP_MFSCLEAN_FINDPEAK_CASA = 1
+SDP_HIP_STOKES_IQUV = 0
+SDP_HIP_STOKES_I = 1
 
 c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
@@ -210,6 +212,18 @@ SIGNATURES = {
         c_vp, c_vp, c_vp, c_vp,                     # windowstack, sensitivity, hsmmpsf, ihsmmpsf (host)
         c_int, c_dbl, c_dbl, c_int,                 # findpeak, gain, absthresh, niter
         ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_vp, c_vp] + _ERR,  # done, reason, counts (host)
+    "sdp_hip_vis_average_channels": [
+        c_i64, c_int, c_int, c_int, c_int,        # nrows, nchan, npol, group, variant
+        c_vp, c_int, c_vp, c_vp, c_vp, c_int,     # vis, dtype, weight, imaging_weight, flags, bytes
+        c_vp, c_vp, c_vp, c_vp, c_int, c_vp] + _ERR,  # outputs, flags_out bytes, stream
+    "sdp_hip_vis_to_stokes": [
+        c_i64, c_int, c_int, c_vp, c_int,         # nsamples, npol, mode, vis, dtype
+        c_vp, c_vp, c_vp, c_int, c_vp,            # weight, imaging_weight, flags, bytes, matrix (host)
+        c_vp, c_vp, c_vp, c_vp, c_int, c_vp] + _ERR,  # outputs, flags_out bytes, stream
+    "sdp_hip_vis_remove_continuum": [
+        c_i64, c_int, c_int, c_vp, c_int,         # nrows, nchan, npol, vis, dtype
+        c_vp, c_vp, c_int, c_vp, c_vp, c_int,     # weight, flags, bytes, x, mask, degree
+        c_vp, c_int, c_vp, c_vp] + _ERR,          # rank_list, capacity, rank_count, stream
 }
 
 _lock = threading.Lock()

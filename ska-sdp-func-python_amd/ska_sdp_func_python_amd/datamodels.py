@@ -385,6 +385,12 @@ class _VisAcc:
         return int(self._v._vars["time"].shape[0])
 
     @property
+    def nvis(self):
+        """The number of time rows (the reference's remove_continuum_visibility
+        loops over it, visibility/operations.py:129)."""
+        return int(self._v._vars["vis"].shape[0])
+
+    @property
     def nbaselines(self):
         return int(self._v._vars["vis"].shape[1])
 
@@ -520,6 +526,11 @@ class Visibility(Dataset):
     def baselines(self):
         return _Plain(self.attrs["baselines"])
 
+    def __getitem__(self, name):
+        if name == "baselines":  # a coordinate in ska-sdp-datamodels: vis["baselines"]
+            return self.baselines
+        return super().__getitem__(name)
+
     def copy(self, deep=True, data=None, zero=False):
         return self._copy_with(deep=deep, zero_vars=("vis",) if zero else ())
 
@@ -551,6 +562,12 @@ class Visibility(Dataset):
 class _Plain:
     def __init__(self, data):
         self.data = data
+
+    def __iter__(self):
+        return iter(self.data)
+
+    def __len__(self):
+        return len(self.data)
 
 
 def _ones_like(v, real=False):
