@@ -3,24 +3,62 @@
 // called by the reference's invert_ng / predict_ng
 // (src/ska_sdp_func_python/imaging/ng.py:99-129, :240-289).
 //
-// Pipeline (one stream, two host syncs per call):
-//   k_bounds       fp64 w range / uv extent over the rows
-//   k_bucket<0>    per-visibility fp64 grid coordinates -> bucket key
-//                  (first w plane p0, 2x2 or 16x16 uv cells) and rank in the
-//                  bucket from a wave-level run-length histogram (one atomic
-//                  per run of equal keys)
-//   scan           hipcub exclusive sum over buckets
-//   k_bucket<1>    32-byte visibility records at offs[key] + rank (no atomics)
-//   k_items_*      work items = one bucket, split into <= chunk records
-//   per plane chunk (all planes resident when they fit the budget):
-//     k_grid       one workgroup per item owning an LDS tile of W planes
-//                  x (16+W-1)^2 complex cells, planes split over its waves;
-//                  per record one lane per (u,v) tap does a plain
-//                  ds_read_b64/ds_write_b64 update of the wave's planes; the
-//                  tile is flushed with global float atomics
-//     hipFFT       batched in-place c2c over the planes
-//     k_screen_fwd w-screen phase, real part, fp64 accumulate, grid correction
-//   dirty2ms runs the stages in adjoint order (k_screen_adj, FFT, k_degrid).
+// One translation unit.  Its first two stages are read through headers:
+// wstack_types.h (constants, Geo, records, work items, ES kernel, coordinates
+// and bucket keys) and wstack_bucket.h (k_bounds, the typed loads, the
+// single-level bucketing kernels); the in-LDS FFT is wstack_fx_fft.h.  The
+// rest follows below under its section banners, in this order: work items
+// and sub-sort, fp32 gridder / degridder, plane kernels (transposes, screens,
+// fused x-FFT), write-back, fp64 records, two-level bucketing, fp64 gridders
+// / degridder, host side (state, plan, launchers, plane and bucketing
+// drivers), call drivers, C ABI.
+//
+// An invert (ms2dirty), in call order:
+//   plan_geometry      k_bounds: w range and uv extent; support, padded
+//                      grid, plane layout, Hermitian fold, bucket window,
+//                      bucketing route, Plan flags, resident planes
+//                      (grid_budget_bytes)
+//   bucket_all         records in cell order and work items, by one of the
+//                      routes below; subsort_items on the coarse route
+//   per chunk of resident planes (invert_planes):
+//     zero_band
+//     grid_f32         k_grid_mfma_pad (Plan::pad4 or Plan::subpad)
+//     grid_f64         k_grid_f64_mfma (Plan::pad64) or k_grid_f64
+//     core_merge       fp32: the fp64 uv core into the planes
+//     fft_rows_y       hipFFT over the band rows
+//     tr_grid_to_t     k_tr_grid_to_t*
+//     xfft_screen_fwd  k_xfft_screen_fwd (xfft_log2 != 0), or hipFFT and
+//                      k_screen_fwd_t: w screen, real part, fp64
+//                      accumulation, grid correction
+// A predict (dirty2ms) runs the adjoint stages:
+//   plan_geometry, bucket_all, subsort_items as above (records carry no value)
+//   per chunk of resident planes (plane_stage; with resident planes it runs
+//   on the auxiliary stream beside the bucketing):
+//     zero_band, screen_adj_xfft (k_screen_adj_xfft, or k_screen_adj_t and
+//     hipFFT), tr_t_to_grid, fft_rows_y
+//     degrid_f32       k_degrid_mfma
+//     degrid_f64       k_degrid_f64_mfma (Plan::mfma64)
+//   finalize_vis       k_finalize*, unless the degridder wrote the
+//                      visibilities itself (Plan::vdirect, fp64)
+//
+// Bucketing routes (chosen in plan_geometry_once):
+//   two-level, one-cell    g.tiled = 1, g.sub = 1: bucket_tiled, k_t_*.
+//                          Inverts and fp64 predicts whose window has <=
+//                          kMaxBins 64 x 64-cell bins and whose padded record
+//                          total fits 32 bits; not a kept bucketing
+//                          (SDP_HIP_BUCKET2 = 0: never, 2: always).
+//   single-level, one-cell g.tiled = 0, g.sub = 1: bucket_part, k_bucket /
+//                          k_bucket_f64 / k_bucket_pols, k_group_*.  While
+//                          first planes x window cells <= kMaxCellKeys.
+//   coarse + sub-sort      g.sub = 16, fp32 only: bucket_part with 16x16-cell
+//                          keys, k_items_*, then subsort_items: k_subsort
+//                          (predict) or k_subsort_pad (invert, Plan::subpad).
+//                          Larger grids, or SDP_HIP_BUCKET=16.
+//
+// fp32 / fp64: epsilon >= 1e-7 (or SDP_HIP_FP32) runs W in [2, 8], VisRec /
+// RecC records, c64 planes and the fp32 MFMA kernels; a smaller epsilon sets
+// Plan::f64: W in [9, 16], VisRec64 / Rec64 records, c128 planes, Z2Z FFTs,
+// the fp64 kernels and the unfused screens.
 //
 // Numerics: coordinates, plane positions and phases in fp64; kernel taps and
 // grid values in fp32; image accumulation and corrections in fp64.  ES kernel
@@ -43,931 +81,11 @@
 
 #include "sdp_common.h"
 #include "wstack_fx_fft.h"
+#include "wstack_types.h"
+#include "wstack_bucket.h"
 
 namespace sdp {
 namespace wstack {
-
-constexpr double kCLight = 299792458.0;
-constexpr int kTileCoarse = 16;  // bucket edge (cells) of large grids (sub-sorted by cell)
-// one-cell buckets ordered x-pair major (key tile = ((ic >> 1) * ngy + jc) *
-// 2 + (ic & 1)), so a bucket's records share their footprint origin and 16
-// consecutive buckets form one 2 x 8-cell work-item region
-constexpr int kTileCell = 1;
-constexpr int kGroupCell = 16;
-constexpr int64_t kMaxCellKeys = (int64_t)1 << 28;
-constexpr int kGridAlign = 16;   // padded grid edges are multiples of this
-constexpr int kChunkMin = 1024;   // records per work item: chosen per call in
-constexpr int kChunkMax = 8192;   // [kChunkMin, kChunkMax] (chunk_size())
-constexpr int kMaxW = 8;
-constexpr int kPhiTab = 8193;  // Phi(xi) table on xi in [0, 0.5]
-constexpr int kFftBatchMax = 16;                      // planes per FFT batch
-constexpr size_t kFftBatchBytes = (size_t)16 << 30;  // y-spectra buffers per batch
-
-struct Geo {
-    int W;
-    float beta, inv_half_w, beta_l2e;
-    int nx, ny, ngx, ngy;
-    double px, py;
-    int do_w, nplanes, nps;  // nps = number of distinct first planes
-    double w0, dw, s0;
-    int sub, nty, ntiles;  // bucket edge in cells, buckets per window column, buckets
-    // bucket window: the footprint origins of all visibilities lie in cells
-    // [wx0, wx0 + wnx) x [wy0, wy0 + wny) (16-aligned), so only the window's
-    // buckets are histogrammed, scanned and itemised
-    int wx0, wy0, wnx, wny;
-    int grp;               // consecutive buckets (along y) per work-item group
-    // keys per bucket (16x16-cell buckets: a power of 2 > 1): the count pass
-    // spreads a bucket's histogram counter over `salt` adjacent counters by
-    // row, so the uv core's hot buckets take several memory-side atomic
-    // streams; the sub-buckets are adjacent, so the bucket stays contiguous
-    int salt;
-    double su;  // sign applied to u and w (-1 with SDP_HIP_FLIP_UW)
-    int nchan;
-    int64_t nrow;
-    // one-cell keys: blocks of bx x 8 cells (bx = 2, 4 or 8; bxs = log2 bx),
-    // each bx / 2 groups of 2 x 8 cells, consecutive in the key order
-    int bx, bxs;
-    // w slab (SDP_HIP_W_SLAB): this call grids only the visibilities whose
-    // first plane lies in [slab_lo, slab_lo + nps) of the sequence's layout of
-    // nps_all first planes; w0 is then the slab's first plane, and the others
-    // are skipped without being counted as out of bounds
-    int slab, slab_lo, nps_all;
-    // two-level bucketing of one-cell keys (tiled = 1): the window is cut into
-    // tlx x tly bins of 64 x 64 cells per first plane (nbins in all); the
-    // keys of a bin are contiguous (bin-major, 4096 per bin)
-    int tiled, tlx, tly, nbins;
-    double inv_nchan;  // 1 / nchan (the two-level passes' row = v / nchan)
-    // folded per-visibility factors (geo_factors): a = u_m s kax, b = v_m s
-    // kby, fractional plane pw = w_m s kpw - kpw0 of the FULL layout (a w
-    // slab subtracts its first plane as an integer, so slabs partition the
-    // visibilities exactly) -- no fp64 division per visibility
-    double kax, kby, kpw, kpw0;
-    // Hermitian fold (invert only, plan_geometry): a visibility with
-    // su * u < 0 is gridded at (-u, -v, -w) with its value conjugated -- the
-    // same real part of the image -- so every footprint lies in the grid rows
-    // from ngx / 2 - W / 2 - 1 up and the plane passes run over half the band.
-    // The plane layout (w0, dw, nplanes, nps) is that of the unfolded w range.
-    int fold;
-};
-
-struct __attribute__((aligned(32))) VisRec {
-    float cre, cim;    // gridding: vis*wgt*exp(2 pi i w s0); degridding: wgt*exp(-2 pi i w s0)
-    float fu, fv, fw;  // offset of the first tap from the exact position (cells/planes)
-    uint32_t ij;       // footprint start in the centred grid: ic0 | jc0 << 16
-    uint32_t p0;       // first w plane
-    uint32_t idx;      // row * nchan + chan
-};
-static_assert(sizeof(VisRec) == 32, "record layout");
-
-// 16-byte record of the 4-padded invert (k_grid_mfma_pad): the value and the
-// footprint offsets as fixed-point fractions, e = (1 - W/2) - f in [0, 1):
-// u in lo[0:21), v in lo[21:32) | hi[0:10), w in hi[10:32) (steps of 2^-21,
-// 2^-21, 2^-22 cells / planes, i.e. rounding errors <= 2.4e-7 / 1.2e-7 --
-// fp32 offsets near 3.5 round to 1.2e-7).  The cell and the first plane are
-// those of the record's bucket, so the record does not carry them.
-struct __attribute__((aligned(16))) RecC {
-    float cre, cim;
-    uint32_t lo, hi;
-};
-static_assert(sizeof(RecC) == 16, "record layout");
-
-__device__ __forceinline__ uint32_t fix_frac(double e, int bits) {
-    const double q = floor(e * (double)(1u << bits) + 0.5);
-    return (uint32_t)fmin(fmax(q, 0.0), (double)((1u << bits) - 1u));
-}
-
-struct Item {
-    uint32_t b, e, tile, p0;
-};
-
-// Large grids (16x16-cell buckets): work item of one group of 4 2x2-cell
-// buckets (a 2 x 8-cell region) inside a sub-sorted coarse item; records
-// [b, e) ordered by bucket, bucket j of the group ending at o[j] (k_subsort)
-struct FineItem {
-    uint32_t b, e, tile, p0;
-    uint32_t o[16];  // end of bucket j of the group (2x2 buckets: j < 4; cells: j < 16)
-};
-
-// ------------------------------------------------------------------------
-// device helpers
-// ------------------------------------------------------------------------
-static int env_int(const char *name, int dflt) {
-    const char *e = std::getenv(name);
-    return e ? std::atoi(e) : dflt;
-}
-
-// ES kernel exp(beta (sqrt(1 - x^2) - 1)), x = 2t/W; `beta_l2e` = beta*log2(e)
-// so the raw v_exp_f32 (2^x) and v_sqrt_f32 are used directly.
-__device__ __forceinline__ float es_kernel(float t, float inv_half_w, float beta_l2e) {
-    const float x = t * inv_half_w;
-    const float y = 1.0f - x * x;
-    const float e =
-        __builtin_amdgcn_exp2f(beta_l2e * (__builtin_amdgcn_sqrtf(fmaxf(y, 0.0f)) - 1.0f));
-    return y > 0.0f ? e : 0.0f;
-}
-
-// 4-point Lagrange interpolation of the tabulated Phi on [0, 0.5].
-__device__ __forceinline__ double phi_lookup(const double *__restrict__ tab, double xi) {
-    xi = fabs(xi);
-    const double t = xi * (2.0 * (kPhiTab - 1));
-    int k = (int)t;
-    k = min(max(k, 1), kPhiTab - 3);
-    const double f = t - k;
-    const double p0 = tab[k - 1], p1 = tab[k], p2 = tab[k + 1], p3 = tab[k + 2];
-    const double fm1 = f + 1.0, f1 = f - 1.0, f2 = f - 2.0;
-    return -p0 * f * f1 * f2 / 6.0 + p1 * fm1 * f1 * f2 / 2.0 - p2 * fm1 * f * f2 / 2.0 +
-           p3 * fm1 * f * f1 / 6.0;
-}
-
-struct Coord {
-    int ic0, jc0, p0;
-    float fu, fv, fw;
-    double du, dv, dw;  // the same offsets in fp64 (RecC encoding)
-    double w;  // w in wavelengths (sign applied)
-    bool ok;
-    bool skip = false;  // w slab: inside the sequence's layout, outside this slab
-    bool conj = false;  // folded (Geo::fold): the record holds the value's conjugate
-};
-
-// the visibility's grid coordinates from its row's uvw (metres) and its
-// frequency
-__device__ __forceinline__ Coord vis_coord_v(const Geo &g, double um, double vm, double wm,
-                                             double s) {
-    Coord c;
-    double ws = wm * s;
-    // (the ORIGINAL w: the writers rotate by the original coordinates' phase
-    // and conjugate the rotated value)
-    c.w = g.su * ws;
-    double a = (um * s) * g.kax;
-    double b = (vm * s) * g.kby;
-    // the fold's one predicate (k_bounds uses the same): u = 0 does not fold
-    if (g.fold && g.su * um < 0.0) {
-        a = -a;
-        b = -b;
-        ws = -ws;
-        c.conj = true;
-    }
-    c.ok = fabs(a) < (double)g.ngx && fabs(b) < (double)g.ngy;
-    if (!c.ok) return c;
-    const double fa = floor(a - 0.5 * g.W), fb = floor(b - 0.5 * g.W);
-    c.du = fa + 1.0 - a;
-    c.dv = fb + 1.0 - b;
-    c.fu = (float)c.du;
-    c.fv = (float)c.dv;
-    // (fa + 1 + ng/2) mod ng: |a| < ng puts it in (-ng, 2 ng), so one
-    // conditional add or subtract is the modulo (no integer division)
-    int ic = (int)fa + 1 + g.ngx / 2, jc = (int)fb + 1 + g.ngy / 2;
-    ic = ic >= g.ngx ? ic - g.ngx : (ic < 0 ? ic + g.ngx : ic);
-    jc = jc >= g.ngy ? jc - g.ngy : (jc < 0 ? jc + g.ngy : jc);
-    c.ic0 = ic;
-    c.jc0 = jc;
-    // the footprint origin must lie in the bucket window and the first plane
-    // in [0, nps): always so when the geometry comes from these
-    // visibilities' own extremes (a margin of >= 2 cells / half a plane), but
-    // a batch of a batched invert is checked against the bounds its caller
-    // gave (out of them it would index outside the histogram or the planes)
-    c.ok = (unsigned)(c.ic0 - g.wx0) < (unsigned)g.wnx &&
-           (unsigned)(c.jc0 - g.wy0) < (unsigned)g.wny;
-    if (g.do_w) {
-        const double pw = fma(ws, g.kpw, -g.kpw0);
-        const double fp = floor(fmin(fmax(pw - 0.5 * g.W, -2.0), 2.0e9));
-        c.dw = fp + 1.0 - pw;
-        c.fw = (float)c.dw;
-        c.p0 = (int)fp + 1 - g.slab_lo;
-        const bool in_slab = c.p0 >= 0 && c.p0 < g.nps;
-        c.ok = c.ok && in_slab;
-        if (g.slab) c.skip = !in_slab && (unsigned)(c.p0 + g.slab_lo) < (unsigned)g.nps_all;
-        c.p0 = min(max(c.p0, 0), g.nps - 1);
-    } else {
-        c.p0 = 0;
-        c.fw = 0.0f;
-        c.dw = 0.0;
-    }
-    return c;
-}
-
-__device__ __forceinline__ Coord vis_coord(const Geo &g, const double *__restrict__ uvw,
-                                           int64_t rs, int64_t row, double f) {
-    return vis_coord_v(g, uvw[row * rs], uvw[row * rs + 1], uvw[row * rs + 2], f / kCLight);
-}
-
-// w slab: the visibility's first plane (computed exactly as vis_coord does)
-// lies in the sequence's layout but outside this call's slab -- tested before
-// anything else of the visibility is read
-__device__ __forceinline__ bool slab_out_v(const Geo &g, double wm, double s) {
-    const double pw = fma(wm * s, g.kpw, -g.kpw0);
-    const int p0 = (int)floor(fmin(fmax(pw - 0.5 * g.W, -2.0), 2.0e9)) + 1 - g.slab_lo;
-    return (p0 < 0 || p0 >= g.nps) && (unsigned)(p0 + g.slab_lo) < (unsigned)g.nps_all;
-}
-
-__device__ __forceinline__ bool slab_out(const Geo &g, const double *__restrict__ uvw, int64_t rs,
-                                         int64_t row, double f) {
-    return slab_out_v(g, uvw[row * rs + 2], f / kCLight);
-}
-
-// p0-major bucket keys: the items of a range of first planes are contiguous.
-// One-cell keys inside a plane: block (x-major), x pair in the block, y, x
-// parity -- 16 consecutive keys are a group of 2 x 8 cells.
-// Two-level (tiled) one-cell keys: bin = (first plane, 64 x 64-cell tile of
-// the window), then inside the bin: x pair (32), y block of 8 (8), and the
-// cell of the 2 x 8-cell group, (y & 7) * 2 + (x & 1) -- 16 consecutive keys
-// are again one group, 256 groups per bin.
-constexpr int kTile = 64;
-constexpr int kBinCells = kTile * kTile;
-__device__ __forceinline__ unsigned tiled_key(const Geo &g, const Coord &c) {
-    const int ic = c.ic0 - g.wx0, jc = c.jc0 - g.wy0;
-    const int tile = (ic >> 6) * g.tly + (jc >> 6);
-    const int lx = ic & 63, ly = jc & 63;
-    const unsigned local = ((unsigned)(((lx >> 1) << 3) | (ly >> 3)) << 4) |
-                           (unsigned)((ly & 7) << 1) | (unsigned)(lx & 1);
-    return ((unsigned)c.p0 * (unsigned)(g.tlx * g.tly) + (unsigned)tile) * (unsigned)kBinCells +
-           local;
-}
-
-__device__ __forceinline__ unsigned coord_key(const Geo &g, const Coord &c, int64_t row) {
-    if (g.tiled) return tiled_key(g, c);
-    const int ic = c.ic0 - g.wx0, jc = c.jc0 - g.wy0;
-    const int tile =
-        g.sub == kTileCell
-            ? ((((ic >> g.bxs) * (g.wny >> 3) + (jc >> 3)) << (g.bxs - 1)) + ((ic & (g.bx - 1)) >> 1)) *
-                      16 + (jc & 7) * 2 + (ic & 1)
-            : (ic / g.sub) * g.nty + (jc / g.sub);
-    return ((unsigned)c.p0 * (unsigned)g.ntiles + (unsigned)tile) * (unsigned)g.salt +
-           ((unsigned)row & (unsigned)(g.salt - 1));
-}
-
-// ------------------------------------------------------------------------
-// kernels: geometry and bucketing
-// ------------------------------------------------------------------------
-// uvw extent: per-block partials (no atomics), reduced by one block after
-constexpr int kBoundsBlocks = 1024;
-
-// raw extremes in metres (min/max of su*w, max |u|, max |v|, and min/max of
-// the Hermitian-folded su*w: negated on the rows with su*u < 0); the host
-// scales them by the frequency range (w*s is monotonic in w for s > 0)
-__global__ __launch_bounds__(256) void k_bounds(const double *__restrict__ uvw, int64_t rs,
-                                                int64_t nrow, double su,
-                                                double *__restrict__ part) {
-    __shared__ double red[6][4];
-    double wmn = 1e300, wmx = -1e300, umx = 0.0, vmx = 0.0, fmn = 1e300, fmx = -1e300;
-    for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < nrow;
-         r += (int64_t)gridDim.x * blockDim.x) {
-        const double u = uvw[r * rs], v = uvw[r * rs + 1], w = su * uvw[r * rs + 2];
-        wmn = fmin(wmn, w);
-        wmx = fmax(wmx, w);
-        umx = fmax(umx, fabs(u));
-        vmx = fmax(vmx, fabs(v));
-        const double wf = su * u < 0.0 ? -w : w;
-        fmn = fmin(fmn, wf);
-        fmx = fmax(fmx, wf);
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        wmn = fmin(wmn, __shfl_xor(wmn, o));
-        wmx = fmax(wmx, __shfl_xor(wmx, o));
-        umx = fmax(umx, __shfl_xor(umx, o));
-        vmx = fmax(vmx, __shfl_xor(vmx, o));
-        fmn = fmin(fmn, __shfl_xor(fmn, o));
-        fmx = fmax(fmx, __shfl_xor(fmx, o));
-    }
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[0][wv] = wmn;
-        red[1][wv] = wmx;
-        red[2][wv] = umx;
-        red[3][wv] = vmx;
-        red[4][wv] = fmn;
-        red[5][wv] = fmx;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < 4; ++k) {
-            red[0][0] = fmin(red[0][0], red[0][k]);
-            red[1][0] = fmax(red[1][0], red[1][k]);
-            red[2][0] = fmax(red[2][0], red[2][k]);
-            red[3][0] = fmax(red[3][0], red[3][k]);
-            red[4][0] = fmin(red[4][0], red[4][k]);
-            red[5][0] = fmax(red[5][0], red[5][k]);
-        }
-        for (int k = 0; k < 6; ++k) part[k * kBoundsBlocks + blockIdx.x] = red[k][0];
-    }
-}
-
-// out = {min su*w, max su*w, max|u|, max|v|, min freq, max freq, min and max
-// of the folded su*w}
-__global__ __launch_bounds__(256) void k_bounds_final(int nblocks, const double *__restrict__ part,
-                                                      const double *__restrict__ freq, int nchan,
-                                                      double *__restrict__ out) {
-    __shared__ double red[8][256];
-    double a[8] = {1e300, -1e300, 0.0, 0.0, 1e300, -1e300, 1e300, -1e300};
-    for (int b = threadIdx.x; b < nblocks; b += 256) {
-        a[0] = fmin(a[0], part[b]);
-        a[1] = fmax(a[1], part[kBoundsBlocks + b]);
-        a[2] = fmax(a[2], part[2 * kBoundsBlocks + b]);
-        a[3] = fmax(a[3], part[3 * kBoundsBlocks + b]);
-        a[6] = fmin(a[6], part[4 * kBoundsBlocks + b]);
-        a[7] = fmax(a[7], part[5 * kBoundsBlocks + b]);
-    }
-    for (int c = threadIdx.x; c < nchan; c += 256) {
-        a[4] = fmin(a[4], freq[c]);
-        a[5] = fmax(a[5], freq[c]);
-    }
-    for (int k = 0; k < 8; ++k) red[k][threadIdx.x] = a[k];
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (threadIdx.x < st) {
-            const int t = threadIdx.x;
-            red[0][t] = fmin(red[0][t], red[0][t + st]);
-            red[4][t] = fmin(red[4][t], red[4][t + st]);
-            red[6][t] = fmin(red[6][t], red[6][t + st]);
-            for (int k : {1, 2, 3, 5, 7}) red[k][t] = fmax(red[k][t], red[k][t + st]);
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x < 8) out[threadIdx.x] = red[threadIdx.x][0];
-}
-
-// per-part plan metadata (one buffer, one D2H copy when the host needs it):
-// {nbad lo, nbad hi, nrec, nitems, first item of each first-plane value
-// [nps + 1]}; meta[3] is also the item count persistent launches read
-__global__ void k_part_meta(const unsigned long long *__restrict__ nbad,
-                            const unsigned *__restrict__ nrec, const unsigned *__restrict__ npad,
-                            const unsigned *__restrict__ ioffs, int groups_per_plane, int nps,
-                            unsigned *__restrict__ meta) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k == 0) {
-        meta[0] = (unsigned)(*nbad & 0xffffffffull);
-        meta[1] = (unsigned)(*nbad >> 32);
-        meta[2] = *nrec - (npad ? *npad : 0u);  // gridded visibilities (pads excluded)
-        meta[3] = ioffs[(size_t)nps * groups_per_plane];
-    }
-    if (k <= nps) meta[4 + k] = ioffs[(size_t)k * groups_per_plane];
-}
-
-// Wave-level run-length aggregation: consecutive lanes with equal keys share
-// one atomic on counter[key]; with kScatter each lane gets its slot.
-template <bool kScatter>
-__device__ __forceinline__ unsigned run_reserve(unsigned key, bool valid, unsigned *counter) {
-    const int lane = threadIdx.x & 63;
-    const unsigned prev = __shfl_up(key, 1);
-    const bool start = (lane == 0) || (prev != key);
-    const unsigned long long B = __ballot(start);
-    const unsigned long long above = (lane == 63) ? 0ull : (B & ~((2ull << lane) - 1ull));
-    const int end = above ? (__ffsll((long long)above) - 1) : 64;
-    unsigned base = 0;
-    if (valid && start) base = atomicAdd(&counter[key], (unsigned)(end - lane));
-    if (!kScatter) return 0;
-    const unsigned long long upto = (lane == 63) ? B : (B & ((2ull << lane) - 1ull));
-    const int head = 63 - __clzll((long long)upto);
-    const unsigned hb = __shfl(base, head);
-    return hb + (unsigned)(lane - head);
-}
-
-// Visibility-side prologue fused into the bucketing pass (sdp_hip_ms2dirty_vis,
-// SURVEY.md §8(f) rank 2): flag masking of the visibilities and weights,
-// fp64 weights, the polarisation-frame conversion of the reference's
-// convert_pol_frame (imaging/ng.py:193-198) as one row of its matrix, and
-// the weight sum the reference takes with numpy.sum (ng.py:258, :289).
-struct VisExtra {
-    int64_t vps = 0;           // vis pol stride (elements); vis points at pol 0 when conv
-    int npv = 1;               // vis pols combined
-    bool conv = false;         // vis_eff = sum_k coef_k * vis_k * (1 - flag_k)
-    double cre[4] = {1.0, 0.0, 0.0, 0.0}, cim[4] = {0.0, 0.0, 0.0, 0.0};
-    int wgt_f64 = 0;           // weights are f64 (else f32)
-    const void *flags = nullptr;
-    int fbytes = 0;            // 1 / 4 / 8 byte integer flags at pol 0
-    int64_t frs = 0, fcs = 0, fps = 0;
-    int fpol = 0;              // pol whose flag masks the weight (and the vis when !conv)
-    double *sumwt = nullptr;   // += sum of the effective weights (device, may be null)
-    // shift_vis_to_image with tangent=True (reference imaging/base.py:48-92,
-    // visibility/base.py:27-45, :60-90): phase d = uvw_lambda . (l, m, n-1)
-    // in turns, folded into the record factor as exp(+2 pi i d) for invert
-    // (vis * conj(phasor)) and exp(-2 pi i d) for predict (vis * phasor)
-    bool shift = false;
-    double sl = 0.0, sm = 0.0, sn = 0.0;
-    // SDP_HIP_KEEP_BUCKETS: every in-grid visibility is bucketed (zero
-    // weights add exact zeros), so the bucketing holds for any weights
-    bool all = false;
-};
-
-constexpr int kSumSlots = 1024;
-
-__device__ __forceinline__ double flag_mask(const VisExtra &x, int64_t row, int chan, int pol) {
-    const int64_t i = row * x.frs + chan * x.fcs + pol * x.fps;
-    double f;
-    if (x.fbytes == 8) f = (double)static_cast<const int64_t *>(x.flags)[i];
-    else if (x.fbytes == 4) f = (double)static_cast<const int32_t *>(x.flags)[i];
-    else f = (double)static_cast<const int8_t *>(x.flags)[i];
-    return 1.0 - f;
-}
-
-__device__ __forceinline__ double eff_weight(const void *wgt, int64_t wrs, int64_t wcs,
-                                             const VisExtra &x, int64_t row, int chan) {
-    double w = 1.0;
-    if (wgt) {
-        const int64_t i = row * wrs + chan * wcs;
-        w = x.wgt_f64 ? static_cast<const double *>(wgt)[i]
-                      : (double)static_cast<const float *>(wgt)[i];
-    }
-    // select, not multiply: a flagged sample's weight is an exact zero even
-    // when the stored weight is NaN or Inf (ducc0 skips zero-weight samples)
-    if (x.fbytes) {
-        const double m = flag_mask(x, row, chan, x.fpol);
-        w = m == 0.0 ? 0.0 : w * m;
-    }
-    return w;
-}
-
-__device__ __forceinline__ double2 load_vis_d(const float2 *p) {
-    const float2 v = *p;
-    return make_double2(v.x, v.y);
-}
-__device__ __forceinline__ double2 load_vis_d(const double2 *p) { return *p; }
-
-__device__ __forceinline__ float2 load_vis(const float2 *p) { return *p; }
-__device__ __forceinline__ float2 load_vis(const double2 *p) {
-    const double2 v = *p;
-    return make_float2((float)v.x, (float)v.y);
-}
-
-// Two passes over the visibilities.  Rank pass (kScatter = false): fp64
-// coordinates -> bucket key, and the visibility's rank inside its bucket
-// from a run-aggregated atomicAdd on the histogram; the rank is stored.
-// Scatter pass: position = offs[key] + rank -- no atomics -- and the 32-byte
-// record is written there.  Invalid visibilities carry key 0xffffffff.
-template <class VT>
-__device__ __forceinline__ float2 eff_vis(const VT *vis, int64_t vrs, int64_t vcs,
-                                          const VisExtra &x, int64_t row, int chan) {
-    const VT *p = vis + row * vrs + chan * vcs;
-    // flagged pols contribute exact zeros (select, not multiply: a NaN in a
-    // flagged visibility must not reach the image)
-    if (!x.conv) {
-        if (!x.fbytes) return load_vis(p);
-        const double m = flag_mask(x, row, chan, x.fpol);
-        if (m == 0.0) return make_float2(0.0f, 0.0f);
-        const double2 v = load_vis_d(p);
-        return make_float2((float)(v.x * m), (float)(v.y * m));
-    }
-    double re = 0.0, im = 0.0;
-    for (int k = 0; k < x.npv; ++k) {
-        if (x.cre[k] == 0.0 && x.cim[k] == 0.0) continue;
-        double m = 1.0;
-        if (x.fbytes) {
-            m = flag_mask(x, row, chan, k);
-            if (m == 0.0) continue;
-        }
-        double2 v = load_vis_d(p + k * x.vps);
-        v.x *= m;
-        v.y *= m;
-        re += x.cre[k] * v.x - x.cim[k] * v.y;
-        im += x.cre[k] * v.y + x.cim[k] * v.x;
-    }
-    return make_float2((float)re, (float)im);
-}
-
-template <class T>
-struct TypeTag {
-    using type = T;
-};
-
-// Runtime value -> template argument: calls f(std::integral_constant<int, k>{})
-// with k = v for v in [Lo, Hi) and k = Hi for every other v, so f's body is
-// instantiated for exactly Lo .. Hi.
-template <int Lo, int Hi, class F>
-inline void dispatch_int(int v, F &&f) {
-    if constexpr (Lo < Hi) {
-        if (v != Lo) return dispatch_int<Lo + 1, Hi>(v, f);
-    }
-    f(std::integral_constant<int, Lo>{});
-}
-
-template <class VT>
-__device__ __forceinline__ double2 eff_vis_d(const VT *vis, int64_t vrs, int64_t vcs,
-                                             const VisExtra &x, int64_t row, int chan) {
-    const VT *p = vis + row * vrs + chan * vcs;
-    if (!x.conv) {
-        if (!x.fbytes) return load_vis_d(p);
-        const double m = flag_mask(x, row, chan, x.fpol);
-        if (m == 0.0) return make_double2(0.0, 0.0);
-        const double2 v = load_vis_d(p);
-        return make_double2(v.x * m, v.y * m);
-    }
-    double re = 0.0, im = 0.0;
-    for (int k = 0; k < x.npv; ++k) {
-        if (x.cre[k] == 0.0 && x.cim[k] == 0.0) continue;
-        double m = 1.0;
-        if (x.fbytes) {
-            m = flag_mask(x, row, chan, k);
-            if (m == 0.0) continue;
-        }
-        double2 v = load_vis_d(p + k * x.vps);
-        v.x *= m;
-        v.y *= m;
-        re += x.cre[k] * v.x - x.cim[k] * v.y;
-        im += x.cre[k] * v.y + x.cim[k] * v.x;
-    }
-    return make_double2(re, im);
-}
-
-struct TLoad {
-    uint32_t row, chan;
-    double um, vm, wm, s, wd;  // s = frequency / c (fsc[chan]: the same division as vis_coord)
-    double keep;               // 1 - flag of the weight's pol (1 without flags)
-    bool live;
-};
-
-// The weight and flag element types are compile-time in the bucketing
-// passes -- WT: 4 = f32, 8 = f64 (no weights: a device 1.0f with zero
-// strides); FB: 0 = no flags, 1 = int8, 8 = int64 flags (int32 flags are
-// widened to int64 first, k_widen_flags) -- and a lane's visibilities load
-// from clamped, in-bounds indices with no branch before their first use:
-// all of a lane's visibilities' loads (uvw, frequency scale, weight, flag,
-// and in the value pass the visibility) are in flight together.  A runtime switch on the
-// types, with each load behind its own branch and a `live` test, had put a
-// wait for every load before the next one issued (C2 count pass: ~200
-// instructions and four serialised memory round trips per visibility).
-template <int WT, int FB>
-__device__ __forceinline__ TLoad t_load(const Geo &g, int64_t v, int64_t vend,
-                                        const double *__restrict__ uvw, int64_t rs,
-                                        const double *__restrict__ fsc,
-                                        const void *__restrict__ wgt, int64_t wrs, int64_t wcs,
-                                        const VisExtra &x) {
-    TLoad L;
-    L.live = v < vend;
-    const uint32_t v32 = (uint32_t)(L.live ? v : vend - 1), nc = (uint32_t)g.nchan;
-    // row = v / nchan through the fp64 reciprocal (exact to one step, then
-    // corrected), not an integer division
-    uint32_t r32 = (uint32_t)((double)v32 * g.inv_nchan);
-    if ((uint64_t)r32 * nc > v32) --r32;
-    else if ((uint64_t)(r32 + 1u) * nc <= v32) ++r32;
-    L.row = r32;
-    L.chan = v32 - r32 * nc;
-    const double *p = uvw + (int64_t)L.row * rs;
-    L.um = p[0];
-    L.vm = p[1];
-    L.wm = p[2];
-    L.s = fsc[L.chan];
-    double w;
-    const int64_t wi = (int64_t)L.row * wrs + (int64_t)L.chan * wcs;
-    if constexpr (WT == 8) w = static_cast<const double *>(wgt)[wi];
-    else w = (double)static_cast<const float *>(wgt)[wi];
-    L.keep = 1.0;
-    if constexpr (FB != 0) {
-        using FT = typename std::conditional<FB == 8, int64_t, int8_t>::type;
-        L.keep = 1.0 - (double)static_cast<const FT *>(
-                           x.flags)[(int64_t)L.row * x.frs + (int64_t)L.chan * x.fcs + x.fpol * x.fps];
-        // select, not multiply: a flagged sample's weight is an exact zero
-        // even when the stored weight is NaN or Inf
-        w = L.keep == 0.0 ? 0.0 : w * L.keep;
-    }
-    L.wd = L.live ? w : 0.0;
-    return L;
-}
-
-// int32 flags of a two-level pass as int64 (FB = 8): a contiguous
-// [nrow, nchan, npol] copy (one element for a zero-stride broadcast)
-__device__ float g_unit_weight = 1.0f;  // the weights of a call without weights
-template <class FT>
-__global__ void k_widen_flags(const FT *__restrict__ src, int64_t frs, int64_t fcs, int64_t fps,
-                              int64_t nrow, int nchan, int npol, int64_t *__restrict__ dst) {
-    const int64_t n = nrow * nchan * (int64_t)npol;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-         i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t rc = i / npol, row = rc / nchan;
-        const int pol = (int)(i - rc * npol), chan = (int)(rc - row * nchan);
-        dst[i] = (int64_t)src[row * frs + chan * fcs + pol * fps];
-    }
-}
-
-// A pol conversion's visibility (x.conv) for the typed passes: every used
-// pol's value and flag are loaded before any is combined.  The generic
-// eff_vis / eff_vis_d load a pol's flag, branch on it and only then load its
-// value, pol after pol -- serialised memory round trips (the 4-pol MFS value
-// pass ran at 1.5 TB/s).  Coefficients are uniform, flags selected, not
-// multiplied: a NaN in a flagged pol must not reach the image.
-template <class VT, int FB>
-__device__ __forceinline__ double2 conv_vis(const VT *vis, int64_t vrs, int64_t vcs,
-                                            const VisExtra &x, uint32_t row, uint32_t chan) {
-    using FT = typename std::conditional<FB == 8, int64_t, int8_t>::type;
-    const VT *p = vis + (int64_t)row * vrs + (int64_t)chan * vcs;
-    VT v[4];
-    FT f[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        v[k] = VT{};
-        f[k] = 0;
-        if (k < x.npv && (x.cre[k] != 0.0 || x.cim[k] != 0.0)) {
-            v[k] = p[k * x.vps];
-            if constexpr (FB != 0)
-                f[k] = static_cast<const FT *>(
-                    x.flags)[(int64_t)row * x.frs + (int64_t)chan * x.fcs + k * x.fps];
-        }
-    }
-    double re = 0.0, im = 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (k < x.npv && (x.cre[k] != 0.0 || x.cim[k] != 0.0)) {
-            const double m = 1.0 - (double)f[k];
-            const double vx = m == 0.0 ? 0.0 : (double)v[k].x * m;
-            const double vy = m == 0.0 ? 0.0 : (double)v[k].y * m;
-            re += x.cre[k] * vx - x.cim[k] * vy;
-            im += x.cre[k] * vy + x.cim[k] * vx;
-        }
-    }
-    return make_double2(re, im);
-}
-
-// the visibility's value in two phases: `load` issues the loads (the
-// visibility from clamped indices, beside the lane's other loads), `value`
-// combines them after every load is in flight.  Without a pol conversion the
-// weight pol's flag (TLoad::keep) masks it; a pol conversion (x.conv, the
-// 4-pol frames) reads its pols and flags in `value`.
-template <class VT, int KIND, bool kGrid, int FB>
-struct TVal {
-    using type = typename std::conditional<KIND >= 2, double2, float2>::type;
-    __device__ static __forceinline__ VT load(const VT *vis, int64_t vrs, int64_t vcs,
-                                              const VisExtra &x, const TLoad &L) {
-        VT raw{};
-        if constexpr (kGrid)
-            if (vis && !x.conv) raw = vis[(int64_t)L.row * vrs + (int64_t)L.chan * vcs];
-        return raw;
-    }
-    __device__ static __forceinline__ type value(const VT *vis, int64_t vrs, int64_t vcs,
-                                                 const VisExtra &x, const TLoad &L, VT raw) {
-        type xv;
-        xv.x = 1;
-        xv.y = 0;
-        if constexpr (kGrid) {
-            if (!vis) return xv;  // (unit visibilities: the PSF)
-            if (x.conv) {
-                const double2 d = conv_vis<VT, FB>(vis, vrs, vcs, x, L.row, L.chan);
-                xv.x = d.x;
-                xv.y = d.y;
-                return xv;
-            }
-            const double2 v = make_double2((double)raw.x, (double)raw.y);
-            if constexpr (FB == 0) {
-                xv.x = v.x;
-                xv.y = v.y;
-            } else {
-                // select, not multiply: a NaN in a flagged visibility must not
-                // reach the image
-                const double m = L.keep;
-                xv.x = m == 0.0 ? 0.0 : v.x * m;
-                xv.y = m == 0.0 ? 0.0 : v.y * m;
-            }
-        }
-        return xv;
-    }
-};
-
-// One visibility of k_bucket (single-level bucketing: the fp32 predict, kept
-// buckets, large grids).  Its loads -- uvw, frequency scale, weight, flag,
-// and in the value pass its rank and visibility -- are issued together from
-// clamped indices (t_load<WT, FB>, TVal), before any of them is used.
-template <class VT, bool kScatter, bool kGrid, bool kCompact, int WT, int FB>
-__device__ __forceinline__ void bucket_one(const Geo &g, int64_t v, int64_t nvis,
-                                           const double *__restrict__ uvw, int64_t uvw_rs,
-                                           const double *__restrict__ fsc,
-                                           const VT *__restrict__ vis, int64_t vrs, int64_t vcs,
-                                           const void *__restrict__ wgt, int64_t wrs,
-                                           int64_t wcs, const VisExtra &x, double *sw_slots,
-                                           unsigned *counter, unsigned *__restrict__ rk,
-                                           VisRec *__restrict__ recs, unsigned long long *nbad,
-                                           uint8_t *__restrict__ cls, float2 *__restrict__ zout) {
-    using V = TVal<VT, kCompact ? 0 : 1, kGrid, FB>;
-    const TLoad L = t_load<WT, FB>(g, v, nvis, uvw, uvw_rs, fsc, wgt, wrs, wcs, x);
-    const int64_t vg = (int64_t)L.row * g.nchan + L.chan;  // row * nchan + chan
-    // (a w-slab call's outsiders: no rank stored, no weight summed)
-    const bool outside = L.live && g.slab && slab_out_v(g, L.wm, L.s);
-    const double wd = outside ? 0.0 : L.wd;
-    const float wt = (float)wd;
-    if (kScatter) {
-        const unsigned mine = rk[vg];
-        const VT raw = V::load(vis, vrs, vcs, x, L);
-        if (sw_slots) {
-            // weight sum of a reused bucketing (SDP_HIP_REUSE_BUCKETS): the
-            // count pass did not run, so the value pass sums the weights
-            double ws = wd;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) ws += __shfl_xor(ws, o, 64);
-            if ((threadIdx.x & 63) == 0 && ws != 0.0)
-                atomicAdd(&sw_slots[(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) &
-                                    (kSumSlots - 1)],
-                          ws);
-        }
-        if (!L.live || outside || mine == 0xffffffffu) return;
-        const Coord c = vis_coord_v(g, L.um, L.vm, L.wm, L.s);
-        const unsigned pos = counter[coord_key(g, c, L.row)] + mine;
-        float cr = wt, ci = 0.0f;
-        if (kGrid) {
-            // a zero-weight sample (bucketed only by a SDP_HIP_KEEP_BUCKETS
-            // plan, for the other pols) is an exact zero whatever its
-            // visibility holds
-            const float2 xv = V::value(vis, vrs, vcs, x, L, raw);
-            cr = wt != 0.0f ? xv.x * wt : 0.0f;
-            ci = wt != 0.0f ? xv.y * wt : 0.0f;
-        }
-        if (g.do_w || x.shift) {
-            double ph = g.do_w ? c.w * g.s0 : 0.0;
-            if (x.shift) ph += (L.um * x.sl + L.vm * x.sm + L.wm * x.sn) * L.s;
-            ph -= rint(ph);
-            float sn, cs;
-            sincospif((float)(2.0 * ph), &sn, &cs);
-            if (!kGrid) sn = -sn;
-            const float r_ = cr * cs - ci * sn, i_ = cr * sn + ci * cs;
-            cr = r_;
-            ci = i_;
-        }
-        if (kGrid && c.conj) ci = -ci;  // (folded: after the rotation)
-        if (kCompact) {
-            // RecC: offsets as fractions of (1 - W/2) - offset (do_w off: w = 0)
-            const double base = 1.0 - 0.5 * g.W;
-            const uint32_t qu = fix_frac(base - c.du, 21), qv = fix_frac(base - c.dv, 21);
-            const uint32_t qw = g.do_w ? fix_frac(base - c.dw, 22) : 0u;
-            RecC rc;
-            rc.cre = cr;
-            rc.cim = ci;
-            rc.lo = qu | (qv << 21);
-            rc.hi = (qv >> 11) | (qw << 10);
-            reinterpret_cast<RecC *>(recs)[pos] = rc;
-            // large grids (16x16-cell buckets): the record's cell in its
-            // bucket, for the padded sub-sort (k_subsort_pad)
-            if (cls) cls[pos] = (uint8_t)(((c.ic0 & 15) >> 1) * 32 + (c.jc0 & 15) * 2 + (c.ic0 & 1));
-            return;
-        }
-        VisRec rec;
-        rec.cre = cr;
-        rec.cim = ci;
-        rec.fu = c.fu;
-        rec.fv = c.fv;
-        rec.fw = c.fw;
-        rec.ij = (uint32_t)c.ic0 | ((uint32_t)c.jc0 << 16);
-        rec.p0 = (uint32_t)c.p0;
-        rec.idx = (uint32_t)vg;
-        recs[pos] = rec;
-        return;
-    }
-    // rank pass
-    bool valid = L.live && !outside && (x.all || wt != 0.0f);
-    Coord c;
-    c.ok = false;
-    if (valid) {
-        c = vis_coord_v(g, L.um, L.vm, L.wm, L.s);
-        if (!c.ok) {
-            valid = false;
-            if (!c.skip) atomicAdd(nbad, 1ull);
-        }
-    }
-    const unsigned key = valid ? coord_key(g, c, L.row) : 0xffffffffu;
-    const unsigned rank = run_reserve<true>(key, valid, counter);
-    // only the rank is kept: the scatter pass recomputes the key
-    if (L.live && !outside) rk[vg] = valid ? rank : 0xffffffffu;
-    // a predict writing its visibilities in place zeroes the ones no record
-    // reaches here (the degridder writes every other one)
-    if (zout && L.live && !valid) zout[vg] = make_float2(0.0f, 0.0f);
-    if (sw_slots) {
-        // weight sum: wave reduction, one atomic per wave into a slot
-        double ws = wd;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ws += __shfl_xor(ws, o, 64);
-        if ((threadIdx.x & 63) == 0 && ws != 0.0)
-            atomicAdd(&sw_slots[(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) &
-                                (kSumSlots - 1)],
-                      ws);
-    }
-}
-
-template <class VT, bool kScatter, bool kGrid, bool kCompact, int WT, int FB>
-__global__ void k_bucket(Geo g, int64_t nvis, const double *__restrict__ uvw, int64_t uvw_rs,
-                         const double *__restrict__ fsc, const VT *__restrict__ vis, int64_t vrs,
-                         int64_t vcs, const void *__restrict__ wgt, int64_t wrs, int64_t wcs,
-                         VisExtra x, double *sw_slots, unsigned *counter, unsigned *__restrict__ rk,
-                         VisRec *__restrict__ recs, unsigned long long *nbad,
-                         uint8_t *__restrict__ cls, float2 *__restrict__ zout) {
-    bucket_one<VT, kScatter, kGrid, kCompact, WT, FB>(
-        g, blockIdx.x * (int64_t)blockDim.x + threadIdx.x, nvis, uvw, uvw_rs, fsc, vis, vrs, vcs,
-        wgt, wrs, wcs, x, sw_slots, counter, rk, recs, nbad, cls, zout);
-}
-
-// The image pols of one invert_ng call sharing one bucketing
-// (sdp_hip_ms2dirty_vis_pols): image pol q takes row q of the conversion
-// matrix over the visibility pols, the weights of pol q masked by the flags
-// of pol q, and its own record array.
-struct PolsSpec {
-    int npo = 0;                              // image pols (<= 4)
-    double cre[4][4] = {}, cim[4][4] = {};    // [image pol][vis pol]
-    const void *wgt = nullptr;                // weights [row, chan, pol]
-    int64_t wrs = 0, wcs = 0, wps = 0;
-    RecC *recs[4] = {};
-    double *slots[4] = {};                    // weight-sum slots per image pol, or null
-};
-
-// The value pass of all image pols at once (one-cell 4-padded plans): each
-// visibility's pols, flags and weights are read once and the npo records
-// written at the one position the shared bucketing gives it.  One pass per
-// image pol read the pol-interleaved visibilities, flags and weights whole
-// every time (their cache lines) -- the 4-pol MFS value passes ran 5.7 ms
-// each on C2.  The values are those of the per-pol pass bit for bit: the
-// conversion sum in fp64 rounded to fp32, times the fp32 masked weight, then
-// the record factor.
-template <class VT, int WT, int FB, int NPO>
-__global__ __launch_bounds__(256) void k_bucket_pols(Geo g, int64_t nvis,
-                                                     const double *__restrict__ uvw,
-                                                     int64_t uvw_rs,
-                                                     const double *__restrict__ fsc,
-                                                     const VT *__restrict__ vis, int64_t vrs,
-                                                     int64_t vcs, VisExtra x, PolsSpec ps,
-                                                     const unsigned *__restrict__ counter,
-                                                     const unsigned *__restrict__ rk) {
-    using FT = typename std::conditional<FB == 8, int64_t, int8_t>::type;
-    using WTT = typename std::conditional<WT == 8, double, float>::type;
-    const int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    // (t_load's weight and flag are pol 0's; the loop below reads every pol's)
-    const TLoad L = t_load<WT, FB>(g, v, nvis, uvw, uvw_rs, fsc, ps.wgt, ps.wrs, ps.wcs, x);
-    const int64_t vg = (int64_t)L.row * g.nchan + L.chan;
-    const bool outside = L.live && g.slab && slab_out_v(g, L.wm, L.s);
-    // every load of the visibility before any use
-    const unsigned mine = rk[vg];
-    const VT *pv = vis + (int64_t)L.row * vrs + (int64_t)L.chan * vcs;
-    VT vv[4];
-    FT ff[4];
-    WTT ww[NPO];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        vv[k] = VT{};
-        ff[k] = 0;
-        if (k < x.npv) {
-            vv[k] = pv[k * x.vps];
-            if constexpr (FB != 0)
-                ff[k] = static_cast<const FT *>(
-                    x.flags)[(int64_t)L.row * x.frs + (int64_t)L.chan * x.fcs + k * x.fps];
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < NPO; ++q)
-        ww[q] = static_cast<const WTT *>(
-            ps.wgt)[(int64_t)L.row * ps.wrs + (int64_t)L.chan * ps.wcs + q * ps.wps];
-    // the masked weights (select: a flagged sample's weight is an exact zero
-    // even when the stored weight is NaN or Inf) and their sums
-    double wd[NPO];
-#pragma unroll
-    for (int q = 0; q < NPO; ++q) {
-        double w = (double)ww[q];
-        if constexpr (FB != 0) {
-            const double keep = 1.0 - (double)ff[q];
-            w = keep == 0.0 ? 0.0 : w * keep;
-        }
-        wd[q] = (L.live && !outside) ? w : 0.0;
-        if (ps.slots[q]) {
-            double ws = wd[q];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) ws += __shfl_xor(ws, o, 64);
-            if ((threadIdx.x & 63) == 0 && ws != 0.0)
-                atomicAdd(&ps.slots[q][(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) &
-                                       (kSumSlots - 1)],
-                          ws);
-        }
-    }
-    if (!L.live || outside || mine == 0xffffffffu) return;
-    const Coord c = vis_coord_v(g, L.um, L.vm, L.wm, L.s);
-    const unsigned pos = counter[coord_key(g, c, L.row)] + mine;
-    float sn = 0.0f, cs = 1.0f;
-    const bool rot = g.do_w || x.shift;
-    if (rot) {
-        double ph = g.do_w ? c.w * g.s0 : 0.0;
-        if (x.shift) ph += (L.um * x.sl + L.vm * x.sm + L.wm * x.sn) * L.s;
-        ph -= rint(ph);
-        sincospif((float)(2.0 * ph), &sn, &cs);
-    }
-    const double base = 1.0 - 0.5 * g.W;
-    const uint32_t qu = fix_frac(base - c.du, 21), qv = fix_frac(base - c.dv, 21);
-    const uint32_t qw = g.do_w ? fix_frac(base - c.dw, 22) : 0u;
-#pragma unroll
-    for (int q = 0; q < NPO; ++q) {
-        double re = 0.0, im = 0.0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (k < x.npv && (ps.cre[q][k] != 0.0 || ps.cim[q][k] != 0.0)) {
-                double m = 1.0;
-                if constexpr (FB != 0) m = 1.0 - (double)ff[k];
-                const double vx = m == 0.0 ? 0.0 : (double)vv[k].x * m;
-                const double vy = m == 0.0 ? 0.0 : (double)vv[k].y * m;
-                re += ps.cre[q][k] * vx - ps.cim[q][k] * vy;
-                im += ps.cre[q][k] * vy + ps.cim[q][k] * vx;
-            }
-        }
-        const float wt = (float)wd[q];
-        const float xr = (float)re, xi = (float)im;
-        const float cr = wt != 0.0f ? xr * wt : 0.0f, ci = wt != 0.0f ? xi * wt : 0.0f;
-        RecC rc;
-        rc.cre = rot ? cr * cs - ci * sn : cr;
-        rc.cim = rot ? cr * sn + ci * cs : ci;
-        if (c.conj) rc.cim = -rc.cim;  // (folded: after the rotation)
-        rc.lo = qu | (qv << 21);
-        rc.hi = (qv >> 11) | (qw << 10);
-        ps.recs[q][pos] = rc;
-    }
-}
 
 __global__ __launch_bounds__(64) void k_sum_slots(const double *__restrict__ slots, double *out) {
     double s = 0.0;

@@ -1,4 +1,4 @@
-"""GPU tests of the invert's Hermitian fold (Geo::fold in csrc/wstack.hip): a
+"""GPU tests of the invert's Hermitian fold (Geo::fold in csrc/wstack_types.h): a
 visibility with u < 0 is gridded at (-u, -v, -w) with its value conjugated,
 so the plane passes run over half the row band.  The dirty image is the real
 part of the transform, so the result is that of the unfolded call.

@@ -1,4 +1,4 @@
-"""The identity the invert's Hermitian fold rests on (csrc/wstack.hip,
+"""The identity the invert's Hermitian fold rests on (csrc/wstack_types.h,
 Geo::fold), pinned on the CPU with the exact direct sums: the dirty image is
 the real part of the transform, so a visibility at (u, v, w) and its conjugate
 at (-u, -v, -w) contribute the same image.  Expected difference 0; bound
