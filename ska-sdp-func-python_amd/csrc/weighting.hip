@@ -262,12 +262,14 @@ __global__ __launch_bounds__(NT) void k_grid_weights(Geom g, int64_t ntiles,
             if (ic != cur_ic || cell.pu != cur.pu || cell.pv != cur.pv || cell.puc != cur.puc ||
                 cell.pvc != cur.pvc) {
                 flush();
-                if (ic != sum_ic) {
-                    flush_sum();
-                    sum_ic = ic;
-                }
                 cur = cell;
                 cur_ic = ic;
+            }
+            // not part of the run test: a tie of another image channel moves
+            // sum_ic while the run it interrupts stays open
+            if (ic != sum_ic) {
+                flush_sum();
+                sum_ic = ic;
             }
 #pragma unroll
             for (int p = 0; p < NP; ++p) {

@@ -128,3 +128,78 @@ def test_divide_visibility_matches_oracle(dtype):
     tol = 1e-12 if dtype == torch.complex128 else 1e-6
     np.testing.assert_allclose(out.vis.data.cpu().numpy(), x, rtol=tol, atol=tol)
     np.testing.assert_allclose(out.weight.data.cpu().numpy(), xwt, rtol=1e-12)
+
+
+# 2x2 gains with small-integer entries whose LU (LAPACK's, restated by
+# k_gain_prep: rows swapped when |c|_1 > |a|_1, l = r (1 / p), u22 = s - l q)
+# is exact, so that a singular one is singular in any evaluation order.
+_PIVOT_GAINS = {
+    "swap": [[1, 3], [2, 4]],                       # |c| > |a|: pivot 2, u22 = 1
+    "swap_complex": [[1j, 1], [2, 2 - 2j]],         # pivot 2, u22 = -i
+    "equal_no_swap": [[2, 1], [-2, 3]],             # |c| == |a|: izamax keeps the first
+    "equal_no_swap_complex": [[1 + 1j, 1], [2, 1j]],
+    "rank1_swap": [[1, 2], [2, 4]],                 # u22 == 0 after the swap
+    "rank1_swap_complex": [[1j, 2j], [2, 4]],
+    "rank1_no_swap": [[2, 4], [1, 2]],              # u22 == 0 without one
+    "a_zero": [[0, 1], [2, 3]],                     # invertible only through the swap
+    "a_zero_singular": [[0, 0], [2, 3]],
+    "first_column_zero": [[0, 1], [0, 2]],          # zero pivot at the first test
+    "identity": [[1, 0], [0, 1]],
+    "no_swap": [[4, 1], [2, 1]],                    # pivot 4, u22 = 1/2
+}
+_SINGULAR = {"rank1_swap", "rank1_swap_complex", "rank1_no_swap", "a_zero_singular",
+             "first_column_zero"}
+
+
+@pytest.mark.parametrize("npol,dtype,flag_dtype", [(2, torch.complex128, torch.int8),
+                                                   (4, torch.complex128, torch.int32),
+                                                   (2, torch.complex64, torch.int32),
+                                                   (4, torch.complex64, torch.int8)])
+def test_gain_inverse_pivot_branches(npol, dtype, flag_dtype):
+    """inverse=True over every branch of the 2x2 LU: the row swap, the tie
+    that does not swap, both singular exits and the back-substitution with and
+    without the swap, against numpy.linalg.inv (calops_oracle._inv2).  One
+    antenna per gain, all baselines with autocorrelations; the second gain
+    channel holds the same matrices in another order.  The weights say which
+    baselines counted as singular, so they are compared exactly."""
+    from ska_sdp_func_python_amd import datamodels as dm
+    from ska_sdp_func_python_amd.calibration import apply_gaintable
+    names = list(_PIVOT_GAINS)
+    mats = np.array([_PIVOT_GAINS[n] for n in names], dtype=complex)
+    nants = len(names)
+    gain = np.stack([mats, np.roll(mats, 5, axis=0)], axis=1)[None]     # [1, nants, 2, 2, 2]
+    _, ok = co._inv2(gain[0])
+    assert np.array_equal(~ok[:, 0], [n in _SINGULAR for n in names])
+    rng = np.random.default_rng(npol)
+    bl = np.stack(np.triu_indices(nants, 0), 1)
+    shape = (3, len(bl), 2, npol)
+    v = rng.normal(size=shape) + 1j * rng.normal(size=shape)
+    if dtype == torch.complex64:
+        v = v.astype(np.complex64).astype(complex)
+    w = rng.uniform(0.5, 2.0, shape)
+    f = (rng.uniform(size=shape) < 0.05).astype(np.int64)
+    time = np.arange(3, dtype=float)
+    pf = {2: "linearnp", 4: "linear"}[npol]
+    vis = vis_from_arrays(np.zeros(shape[:2] + (3,)), [1e8, 1.1e8], v.copy(), weight=w.copy(),
+                          flags=f.copy(), baselines=bl, pf=pf, times=time)
+    vis["vis"] = torch.as_tensor(v, device="cuda").to(dtype)
+    vis["weight"] = torch.as_tensor(w, device="cuda")
+    vis["flags"] = torch.as_tensor(f, device="cuda").to(flag_dtype)
+    gt = dm.GainTable.constructor(gain.copy(), [1.0], [10.0], np.ones(gain.shape),
+                                  np.zeros((1, 2, 2, 2)), [1e8, 1.1e8], dm.PolarisationFrame(pf))
+    expect_v, expect_w = co.apply_gaintable(v, w, f, time, bl, gain, np.array([1.0]),
+                                            np.array([10.0]), True, True)
+    out = apply_gaintable(vis, gt, inverse=True, use_flags=True)
+    got_w = out["weight"].data.cpu().numpy()
+    np.testing.assert_array_equal(got_w, expect_w)
+    # every baseline with a singular gain at either end lost its weight (pol 0
+    # only for npol 2), and no other did
+    bad = ~(ok[bl[:, 0]] & ok[bl[:, 1]])                                 # [nbl, nchan]
+    assert bad.any() and not bad.all()
+    assert np.array_equal(got_w[..., 0] == 0.0, np.broadcast_to(bad, shape[:3]) | (f[..., 0] == 1))
+    if dtype == torch.complex128:
+        tol = dict(rtol=1e-12, atol=1e-14)
+    else:
+        tol = dict(rtol=1e-6, atol=1e-6)
+    assert out["vis"].data.dtype == dtype
+    np.testing.assert_allclose(out["vis"].data.cpu().numpy(), expect_v, **tol)
