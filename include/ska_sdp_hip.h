@@ -775,6 +775,59 @@ int sdp_hip_vis_remove_continuum(int64_t nrows, int nchan, int npol, void *vis,
                                  void *stream, char *errbuf,
                                  size_t errbuf_len);
 
+/*
+ * Sky-component image operations (reference src/ska_sdp_func_python/
+ * sky_component/operations.py).  The image is [nplanes = nchan * npol, ny, nx]
+ * in C order on the device, f32 or f64 (image_dtype), updated in place; every
+ * other array is f64 / integer on the device.  Components are given in pixel
+ * coordinates (origin 0, x = column, y = row).
+ *
+ * insert and restore are gathers over image tiles of SDP_HIP_SKYCOMP_TILE_Y
+ * rows by SDP_HIP_SKYCOMP_TILE_X columns, numbered row-major (tiles_x =
+ * ceil(nx / TILE_X)).  The caller lists each tile's components in CSR form:
+ * tile_comp[tile_ptr[t] .. tile_ptr[t + 1]) are the indices of the components
+ * that tile t must add, in ascending order.  A pixel adds its terms in that
+ * order, each add rounded to the image type, so with the full list the result
+ * is that of numpy's sequential `+=` bit for bit (insert) whatever the number
+ * of components on a pixel.  A component missing from a tile's list is not
+ * added there; an index outside [0, ncomp) is ignored.  ncomp == 0 leaves the
+ * image untouched (the lists are then not read).
+ *
+ * sdp_hip_skycomp_insert: insert_skycomponent (:583-668) with insert_array
+ * (util/array_functions.py:134-178).  Component c owns the window of `window`
+ * rows and columns whose first pixel is origin[c] = (x0, y0) and adds
+ *   flux[c][plane] * ((taps_y[c][i] * taps_x[c][j]) / insertsum[c])
+ * to pixel (y0 + i, x0 + j); window pixels off the image are skipped.
+ * "Nearest" is window 1 with tap 1 and insertsum 1.
+ *
+ * sdp_hip_skycomp_restore: restore_skycomponent (:671-741).  Component c at
+ * xy[c] = (x, y) adds flux[c][plane] * exp(-(a dx^2 + b dx dy + c dy^2)),
+ * dx = column - x, dy = row - y, to every pixel of the tiles that list it.
+ * The caller may leave a component out of a tile's list only where the
+ * exponent's argument exceeds 700 on the whole tile.
+ *
+ * sdp_hip_skycomp_nearest: the label image of voronoi_decomposition
+ * (:744-783): labels[row][col] (int64) = argmin_c hypot(row - y[c], col -
+ * x[c]), the first minimum on ties; ncomp >= 1.
+ */
+#define SDP_HIP_SKYCOMP_TILE_X 32
+#define SDP_HIP_SKYCOMP_TILE_Y 8
+int sdp_hip_skycomp_insert(int nplanes, int ny, int nx, void *image,
+                           int image_dtype, int64_t ncomp, int window,
+                           const int32_t *origin, const double *taps_y,
+                           const double *taps_x, const double *insertsum,
+                           const double *flux, const int64_t *tile_ptr,
+                           const int32_t *tile_comp, void *stream,
+                           char *errbuf, size_t errbuf_len);
+int sdp_hip_skycomp_restore(int nplanes, int ny, int nx, void *image,
+                            int image_dtype, int64_t ncomp, const double *xy,
+                            const double *flux, double a, double b, double c,
+                            const int64_t *tile_ptr, const int32_t *tile_comp,
+                            void *stream, char *errbuf, size_t errbuf_len);
+int sdp_hip_skycomp_nearest(int ny, int nx, int64_t ncomp, const double *xy,
+                            int64_t *labels, void *stream, char *errbuf,
+                            size_t errbuf_len);
+
 #ifdef __cplusplus
 }
 #endif

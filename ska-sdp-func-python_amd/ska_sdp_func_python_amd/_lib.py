@@ -41,6 +41,8 @@ SDP_HIP_MFSCLEAN_FINDPEAK_RASCIL = 0
 SDP_HIP_MFSCLEAN_FINDPEAK_CASA = 1
 SDP_HIP_STOKES_IQUV = 0
 SDP_HIP_STOKES_I = 1
+SDP_HIP_SKYCOMP_TILE_X = 32
+SDP_HIP_SKYCOMP_TILE_Y = 8
 
 c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
@@ -224,6 +226,16 @@ SIGNATURES = {
         c_i64, c_int, c_int, c_vp, c_int,         # nrows, nchan, npol, vis, dtype
         c_vp, c_vp, c_int, c_vp, c_vp, c_int,     # weight, flags, bytes, x, mask, degree
         c_vp, c_int, c_vp, c_vp] + _ERR,          # rank_list, capacity, rank_count, stream
+    "sdp_hip_skycomp_insert": [
+        c_int, c_int, c_int, c_vp, c_int,         # nplanes, ny, nx, image, dtype
+        c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,  # ncomp, window, origin, taps y / x, sum, flux
+        c_vp, c_vp, c_vp] + _ERR,                 # tile_ptr, tile_comp, stream
+    "sdp_hip_skycomp_restore": [
+        c_int, c_int, c_int, c_vp, c_int,         # nplanes, ny, nx, image, dtype
+        c_i64, c_vp, c_vp, c_dbl, c_dbl, c_dbl,   # ncomp, xy, flux, a, b, c
+        c_vp, c_vp, c_vp] + _ERR,                 # tile_ptr, tile_comp, stream
+    "sdp_hip_skycomp_nearest": [
+        c_int, c_int, c_i64, c_vp, c_vp, c_vp] + _ERR,  # ny, nx, ncomp, xy, labels, stream
 }
 
 _lock = threading.Lock()

@@ -1,10 +1,19 @@
-"""apply_beam_to_skycomponent (reference
-src/ska_sdp_func_python/sky_component/operations.py:366-444).
+"""Sky-component operations (reference
+src/ska_sdp_func_python/sky_component/operations.py).
 
-Host logic over a handful of components: each point component's flux is
-multiplied (or, with ``inverse`` and a non-zero beam, divided) by the beam
-pixel its direction projects to (SIN projection, origin 1, Python's
-round-half-even); components off the image get zero flux.
+apply_beam_to_skycomponent (:366-444) is host logic over a handful of
+components: each point component's flux is multiplied (or, with ``inverse``
+and a non-zero beam, divided) by the beam pixel its direction projects to
+(SIN projection, origin 1, Python's round-half-even); components off the
+image get zero flux.
+
+insert_skycomponent (:583-668), restore_skycomponent (:671-741),
+voronoi_decomposition (:744-783) and image_voronoi_iter (:786-815) work on
+the image: the host computes what is O(components) -- pixel locations, fluxes
+per image channel, the interpolation taps -- with the reference's arithmetic,
+and the pixels are updated by csrc/skycomp.hip.  An image whose pixels are a
+device tensor is updated in place and stays on the device; numpy pixels go
+through the device and are updated in place too.
 """
 
 import collections.abc
@@ -12,8 +21,15 @@ import copy
 import logging
 
 import numpy as np
+from scipy import interpolate
 
-from ..datamodels import SkyComponent, skycoord_to_pixel
+from .. import _device, kernels
+from ..datamodels import Image, SkyComponent, skycoord_to_pixel
+from ..image.operations import convert_clean_beam_to_pixels
+
+__all__ = ["apply_beam_to_skycomponent", "insert_skycomponent", "restore_skycomponent",
+           "voronoi_decomposition", "image_voronoi_iter", "insert_function_sinc",
+           "insert_function_L", "insert_function_pswf", "grdsf"]
 
 log = logging.getLogger("func-python-logger")
 
@@ -57,3 +73,309 @@ def apply_beam_to_skycomponent(sc, beam, phasecentre=None, inverse=False):
     if single:
         return newsc[0]
     return newsc
+
+
+# ---- insert functions (util/array_functions.py:102-131, fft_coordinates.py grdsf)
+# Schwab's rational approximation of the spheroidal function (m = 6, alpha = 1):
+# numerator and denominator coefficients in nu^2 - nuend^2 for nu < 0.75 and
+# for 0.75 <= nu <= 1
+_GRDSF_P = np.array([[8.203343e-2, -3.644705e-1, 6.278660e-1, -5.335581e-1, 2.312756e-1],
+                     [4.028559e-3, -3.697768e-2, 1.021332e-1, -1.201436e-1, 6.412774e-2]])
+_GRDSF_Q = np.array([[1.0000000e0, 8.212018e-1, 2.078043e-1],
+                     [1.0000000e0, 9.599102e-1, 2.918724e-1]])
+
+
+def grdsf(nu):
+    """The spheroidal function at the 1-D array ``nu`` (distance to the edge):
+    (the grid-correction function, the gridding function (1 - nu^2) times it);
+    0 beyond nu = 1.  The reference's arithmetic, operation by operation."""
+    nu = np.abs(nu)
+    lower = (nu >= 0.0) & (nu < 0.75)
+    upper = (nu >= 0.75) & (nu <= 1.0)
+    part = np.zeros(len(nu), dtype="int")
+    part[upper] = 1
+    nuend = np.zeros_like(nu)
+    nuend[lower] = 0.75
+    nuend[upper] = 1.0
+    delnusq = nu**2 - nuend**2
+    top = _GRDSF_P[part, 0]
+    for k in range(1, _GRDSF_P.shape[1]):
+        top += _GRDSF_P[part, k] * np.power(delnusq, k)
+    bot = _GRDSF_Q[part, 0]
+    for k in range(1, _GRDSF_Q.shape[1]):
+        bot += _GRDSF_Q[part, k] * np.power(delnusq, k)
+    value = np.zeros_like(nu)
+    ok = bot > 0.0
+    value[ok] = top[ok] / bot[ok]
+    value[nu > 1.0] = 0.0
+    return value, (1 - nu**2) * value
+
+
+def insert_function_sinc(x):
+    """sin(pi x) / (pi x), and -- as in the reference -- 0 at x == 0."""
+    s = np.zeros_like(x)
+    nz = x != 0.0
+    s[nz] = np.sin(np.pi * x[nz]) / (np.pi * x[nz])
+    return s
+
+
+def insert_function_L(x, a=5):
+    """Lanczos: sinc(x) sinc(x / a)."""
+    return insert_function_sinc(x) * insert_function_sinc(x / a)
+
+
+def insert_function_pswf(x, a=5):
+    """The spheroidal gridding function of |x| / a."""
+    return grdsf(abs(x) / a)[1]
+
+
+_INSERT_FUNCTIONS = {"Lanczos": insert_function_L, "Sinc": insert_function_sinc,
+                     "PSWF": insert_function_pswf}
+
+
+def insert_taps(x, y, bandwidth, support, insert_function):
+    """insert_array's host part for one component at pixel (x, y): the window's
+    first pixel (x0, y0), the row and column taps (length 2 * support) and the
+    sum of their outer product, which the weights are divided by."""
+    intx = int(np.round(x))
+    inty = int(np.round(y))
+    fracx = x - intx
+    fracy = y - inty
+    grid = np.arange(-support, support)
+    taps_y = insert_function(bandwidth * (grid - fracy))
+    taps_x = insert_function(bandwidth * (grid - fracx))
+    insertsum = np.sum(np.outer(taps_y, taps_x))
+    assert insertsum > 0, f"Sum of interpolation coefficients {insertsum}."
+    return (intx - support, inty - support), taps_y, taps_x, insertsum
+
+
+# ---- shared host steps -------------------------------------------------------
+def _component_list(sc, who):
+    if not isinstance(sc, collections.abc.Iterable):
+        sc = [sc]
+    sc = list(sc)
+    for comp in sc:
+        if comp.shape != "Point":
+            raise ValueError(f"{who}: Cannot handle shape {comp.shape}")
+    return sc
+
+
+def _image_flux(comp, image_frequency, nchan, npol, as_is_on_equal_frequencies):
+    """The component's flux on the image's channels [nchan, npol]: cubic
+    interpolation in frequency when it has more than one channel (restore:
+    unless its frequencies are the image's within 1e-7), else broadcast."""
+    cfreq = np.asarray(comp.frequency, dtype=float)
+    flux = np.asarray(comp.flux)
+    same = (as_is_on_equal_frequencies and len(cfreq) == len(image_frequency)
+            and np.max(np.abs(cfreq - image_frequency)) < 1e-7)
+    if not same and flux.shape[0] > 1:
+        out = np.zeros([nchan, npol])
+        for pol in range(npol):
+            out[:, pol] = interpolate.interp1d(cfreq, flux[:, pol], kind="cubic")(image_frequency)
+        return out
+    flux = np.asarray(flux, dtype=np.float64)
+    return flux if flux.shape == (nchan, npol) else np.broadcast_to(flux, (nchan, npol))
+
+
+def _check_pixels(pixels, who):
+    if len(pixels.shape) != 4 or str(pixels.dtype).split(".")[-1] not in ("float32", "float64"):
+        raise ValueError(f"{who}: the image must be float32 or float64 [nchan, npol, ny, nx]")
+    return tuple(int(n) for n in pixels.shape)
+
+
+def _update_pixels(pixels, op):
+    """Run ``op`` (in place on a contiguous device tensor) on the image's pixels
+    where they are: a device tensor is updated in its own storage, host pixels
+    travel to the device and back into the same array."""
+    import torch
+    if _device.is_device(pixels):
+        t = pixels if pixels.is_contiguous() else pixels.contiguous()
+        op(t)
+        if t is not pixels:
+            pixels.copy_(t)
+        return
+    t = _device.to_dev(pixels)
+    op(t)
+    if isinstance(pixels, torch.Tensor):
+        pixels.copy_(t.cpu())
+    else:
+        pixels[...] = t.cpu().numpy()
+
+
+# ---- insert_skycomponent -----------------------------------------------------
+def insert_skycomponent(im, sc, insert_method="Nearest", bandwidth=1.0, support=8):
+    """Insert point SkyComponents into an Image, in place (reference :583-668).
+
+    "Nearest" adds each component's flux to the pixel nearest to it
+    (numpy.round, half to even); "Sinc", "Lanczos" and "PSWF" spread it over a
+    window of ``2 * int(support / bandwidth)`` pixels a side with the reference's
+    interpolation functions, normalised to unit sum; any other name acts as
+    "Nearest", as in the reference.  The flux on the image's channels is the
+    component's, cubic-interpolated in frequency when it has more than one
+    channel.  All components are added by one gather kernel in which every
+    pixel adds its terms in component order, so the image is the reference's
+    sequential result bit for bit.
+
+    Where this differs from the reference:
+
+    * a "Sinc" / "Lanczos" / "PSWF" component whose window does not lie wholly
+      on the image (or which has no pixel location) raises ``ValueError`` before
+      any pixel is changed; the reference fails with numpy's broadcast
+      ``ValueError`` after inserting the earlier components, and for a window
+      wholly left of or above the image wraps round silently;
+    * a single-channel component flux is broadcast over the image's channels
+      for every method (the reference: only for "Nearest", ``IndexError``
+      otherwise);
+    * "Nearest" components off the image, or without a pixel location (behind
+      the tangent plane), are skipped, counted and logged as in the reference;
+    * a shape other than "Point" raises ``ValueError`` before any pixel is
+      changed.
+
+    :param im: Image; pixels float64 or float32, numpy or a device tensor
+    :param sc: SkyComponent or list of SkyComponents
+    :param insert_method: "Nearest" | "Sinc" | "Lanczos" | "PSWF"
+    :param bandwidth: fraction of the uv plane to optimise over
+    :param support: support of the interpolation function
+    :return: the same Image
+    """
+    support = int(support / bandwidth)
+    pixels = im["pixels"].data
+    nchan, npol, ny, nx = _check_pixels(pixels, "insert_skycomponent")
+    sc = _component_list(sc, "insert_skycomponent")
+    log.debug("insert_skycomponent: Using insert method %s", insert_method)
+    if not sc:
+        return im
+    image_frequency = np.asarray(im.frequency.data)
+    px, py = skycoord_to_pixel([comp.direction for comp in sc], im.image_acc.wcs, origin=0,
+                               mode="wcs")
+    flux = np.stack([_image_flux(comp, image_frequency, nchan, npol, False) for comp in sc])
+    insert_function = _INSERT_FUNCTIONS.get(insert_method)
+    nbad = 0
+    if insert_function is None:
+        with np.errstate(invalid="ignore"):
+            x, y = np.round(px), np.round(py)
+            on = np.isfinite(x) & np.isfinite(y) & (x >= 0) & (x < nx) & (y >= 0) & (y < ny)
+        nbad = int(len(sc) - np.count_nonzero(on))
+        origin = np.stack([x[on], y[on]], axis=1).astype("int")
+        taps_y = taps_x = np.ones([len(origin), 1])
+        insertsum = np.ones(len(origin))
+        flux = flux[on]
+    else:
+        origin, taps_y, taps_x, insertsum = [], [], [], []
+        for icomp in range(len(sc)):
+            if not (np.isfinite(px[icomp]) and np.isfinite(py[icomp])):
+                raise ValueError(f"insert_skycomponent: component {icomp} has no pixel location")
+            o, ty, tx, s = insert_taps(px[icomp], py[icomp], bandwidth, support, insert_function)
+            if o[0] < 0 or o[1] < 0 or o[0] + 2 * support > nx or o[1] + 2 * support > ny:
+                raise ValueError(
+                    f"insert_skycomponent: the {2 * support}-pixel window of component {icomp} "
+                    f"at pixel ({px[icomp]:.2f}, {py[icomp]:.2f}) does not fit on the image")
+            origin.append(o)
+            taps_y.append(ty)
+            taps_x.append(tx)
+            insertsum.append(s)
+        origin, taps_y, taps_x = np.array(origin), np.array(taps_y), np.array(taps_x)
+        insertsum = np.array(insertsum)
+    if len(origin):
+        _update_pixels(pixels, lambda t: kernels.skycomp_insert(t, origin, taps_y, taps_x,
+                                                                insertsum, flux))
+    if nbad > 0:
+        log.warning("insert_skycomponent: %s components of %s do not fit on image", nbad, len(sc))
+    return im
+
+
+# ---- restore_skycomponent ----------------------------------------------------
+def restore_skycomponent(im, sc, clean_beam=None):
+    """Add point SkyComponents to an Image as clean-beam Gaussians of their
+    flux, in place (reference :671-741).
+
+    Each component adds flux * exp(-(a dx^2 + b dx dy + c dy^2)) about its
+    (fractional) pixel, with a, b, c of the clean beam in pixels (astropy's
+    Gaussian2D).  The flux is the component's as is when its frequencies are
+    the image's within 1e-7, else cubic-interpolated when it has more than
+    one channel, else broadcast.  One kernel adds all components, per pixel
+    in component order; a component is skipped on an image tile only where
+    the exponent's argument exceeds 700 (a factor below 1e-304) on all of it,
+    so a component off the image still adds its tail.  A component without a
+    pixel location (behind the tangent plane) raises ``ValueError``; the
+    reference fills the image with NaN.
+
+    :param im: Image; pixels float64 or float32, numpy or a device tensor
+    :param sc: SkyComponent or list of SkyComponents
+    :param clean_beam: {"bmaj", "bmin", "bpa"} in (deg, deg, deg)
+    :return: the same Image, ``attrs["clean_beam"]`` set
+    """
+    from ..image.deconvolution import _gaussian_coefficients
+    pixels = im["pixels"].data
+    nchan, npol, ny, nx = _check_pixels(pixels, "restore_skycomponent")
+    sc = _component_list(sc, "restore_skycomponent")
+    if clean_beam is None:
+        raise ValueError("restore_skycomponent: the clean_beam must be specified")
+    beam_pixels = convert_clean_beam_to_pixels(im, clean_beam)
+    a, b, c = _gaussian_coefficients(float(beam_pixels[0]), float(beam_pixels[1]),
+                                     float(beam_pixels[2]))
+    if sc:
+        image_frequency = np.asarray(im.frequency.data)
+        px, py = skycoord_to_pixel([comp.direction for comp in sc], im.image_acc.wcs, origin=0,
+                                   mode="wcs")
+        if not (np.isfinite(px).all() and np.isfinite(py).all()):
+            raise ValueError("restore_skycomponent: a component has no pixel location")
+        flux = np.stack([_image_flux(comp, image_frequency, nchan, npol, True) for comp in sc])
+        xy = np.stack([px, py], axis=1)
+        _update_pixels(pixels, lambda t: kernels.skycomp_restore(t, xy, flux, a, b, c))
+    im.attrs["clean_beam"] = clean_beam
+    return im
+
+
+# ---- Voronoi -----------------------------------------------------------------
+def voronoi_decomposition(im, comps):
+    """The Voronoi decomposition of an image by a set of components (reference
+    :744-783): scipy's Voronoi structure of the components' pixel positions
+    (host) and the label image [ny, nx] of each pixel's nearest component,
+    argmin of hypot with the first minimum on ties -- integers, on the
+    image's device when its pixels are a device tensor, else numpy.  As in
+    the reference, the positions are 1-based pixels and are compared with
+    0-based pixel indices.
+
+    :param im: Image
+    :param comps: list of SkyComponents
+    :return: Voronoi structure, label image
+    """
+    from scipy.spatial import Voronoi
+    x, y = skycoord_to_pixel([c.direction for c in comps], im.image_acc.wcs, 1, "wcs")
+    points = [(x_elem, y[i]) for i, x_elem in enumerate(x)]
+    vor = Voronoi(points)
+    pixels = im["pixels"].data
+    ny, nx = int(pixels.shape[2]), int(pixels.shape[3])
+    dev = pixels.device if _device.is_device(pixels) else _device.device()
+    labels = kernels.skycomp_nearest(ny, nx, vor.points, dev)
+    return vor, _device.like_input(labels, pixels)
+
+
+def image_voronoi_iter(im, components):
+    """Generator of the Voronoi regions of ``components`` as full-size mask
+    Images (1.0 inside, 0.0 outside, float64; reference :786-815): region
+    0 .. max label; one all-ones mask for a single component.  The masks of a
+    device image are built on its device."""
+    import torch
+    pixels = im["pixels"].data
+    on_device = _device.is_device(pixels)
+    shape = tuple(int(n) for n in pixels.shape)
+
+    def image_of(mask):
+        return Image.constructor(data=mask, polarisation_frame=im.image_acc.polarisation_frame,
+                                 wcs=im.image_acc.wcs)
+
+    if len(components) == 1:
+        yield image_of(torch.ones(shape, dtype=torch.float64, device=pixels.device) if on_device
+                       else np.ones(shape))
+        return
+    _, labels = voronoi_decomposition(im, components)
+    nregions = int(labels.max()) + 1
+    for region in range(nregions):
+        if on_device:
+            mask = (labels == region).to(torch.float64).expand(shape).contiguous()
+        else:
+            mask = np.zeros(shape)
+            mask[:, :, (labels == region)] = 1.0
+        yield image_of(mask)
