@@ -828,6 +828,44 @@ int sdp_hip_skycomp_nearest(int ny, int nx, int64_t ncomp, const double *xy,
                             int64_t *labels, void *stream, char *errbuf,
                             size_t errbuf_len);
 
+/*
+ * Frequency Taylor terms of image stacks (reference src/ska_sdp_func_python/
+ * image/taylor_terms.py): a small real matrix applied across a stack of image
+ * planes,
+ *   out[k][i] = sum_c weights[k][c] * in[c][i],  0 <= i < npix.
+ * in_planes and out_planes are HOST arrays of nin and nout DEVICE pointers,
+ * one per plane of npix contiguous elements (separately allocated images and
+ * slices of a cube may be mixed); the inputs are all f32 or all f64
+ * (in_dtype), the outputs f64; weights is a host array [nout][nin].  The
+ * library copies the three tables to device scratch; they may be freed when
+ * the call returns.  No output plane may overlap an input or another output.
+ *
+ * Every output element starts from +0.0 and adds its terms in ascending c:
+ * acc = acc + (w[k][c] * (double)in[c][i]), the product and the sum each
+ * rounded once in fp64 -- numpy's `out[k] += in[c] * w`, bit for bit (a -0.0
+ * input gives +0.0).  With min(nin, nout) <= SDP_HIP_MIX_PLANES_REGS every
+ * input plane is read once and every output plane written once; beyond that
+ * the call makes ceil(nout / REGS) passes, each over all inputs, with the
+ * same result.  Planes aligned to 16
+ * bytes are accessed 16 bytes per lane, any other plane element by element.
+ * 1 <= nin, nout <= SDP_HIP_MIX_PLANES_MAX, 1 <= npix <= 2^40.
+ *
+ * nan_seen != NULL: set to 0 if no input element read and no output element
+ * written was NaN, else to SDP_HIP_MIX_NAN_INPUT (an input was NaN),
+ * SDP_HIP_MIX_NAN_OUTPUT (an output was: inf * 0 and inf - inf included) or
+ * their sum; the call then synchronises the stream.  With NULL the call only
+ * enqueues work.
+ */
+#define SDP_HIP_MIX_NAN_INPUT 1
+#define SDP_HIP_MIX_NAN_OUTPUT 2
+#define SDP_HIP_MIX_PLANES_REGS 8
+#define SDP_HIP_MIX_PLANES_MAX 4096
+int sdp_hip_mix_planes(int nin, int nout, int64_t npix,
+                       const void *const *in_planes, int in_dtype,
+                       double *const *out_planes, const double *weights,
+                       int *nan_seen, void *stream, char *errbuf,
+                       size_t errbuf_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,10 @@ SDP_HIP_STOKES_IQUV = 0
 SDP_HIP_STOKES_I = 1
 SDP_HIP_SKYCOMP_TILE_X = 32
 SDP_HIP_SKYCOMP_TILE_Y = 8
+SDP_HIP_MIX_PLANES_REGS = 8
+SDP_HIP_MIX_PLANES_MAX = 4096
+SDP_HIP_MIX_NAN_INPUT = 1
+SDP_HIP_MIX_NAN_OUTPUT = 2
 
 c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
@@ -236,6 +240,9 @@ SIGNATURES = {
         c_vp, c_vp, c_vp] + _ERR,                 # tile_ptr, tile_comp, stream
     "sdp_hip_skycomp_nearest": [
         c_int, c_int, c_i64, c_vp, c_vp, c_vp] + _ERR,  # ny, nx, ncomp, xy, labels, stream
+    "sdp_hip_mix_planes": [
+        c_int, c_int, c_i64, c_vp, c_int,         # nin, nout, npix, in_planes (host), dtype
+        c_vp, c_vp, ctypes.POINTER(c_int), c_vp] + _ERR,  # out_planes, weights (host), nan_seen, stream
 }
 
 _lock = threading.Lock()

@@ -1344,3 +1344,101 @@ def skycomp_nearest(ny, nx, xy, dev):
     _lib.call("sdp_hip_skycomp_nearest", int(ny), int(nx), xy.shape[0], _ptr(pts), _ptr(labels),
               _stream(dev))
     return labels
+
+
+# ---- plane mixing: frequency Taylor terms (sdp_hip_mix_planes) ----------------
+# planes the kernel holds in registers per pixel: with min(nin, nout) at most
+# this, every plane is read once and written once
+MIX_PLANES_REGS = _lib.SDP_HIP_MIX_PLANES_REGS
+MIX_PLANES_MAX = _lib.SDP_HIP_MIX_PLANES_MAX
+MIX_NAN_INPUT = _lib.SDP_HIP_MIX_NAN_INPUT
+MIX_NAN_OUTPUT = _lib.SDP_HIP_MIX_NAN_OUTPUT
+
+
+def _plane_list(x, name):
+    """The planes of a cube (its first axis) or of a list of tensors."""
+    if isinstance(x, torch.Tensor):
+        if x.dim() < 2:
+            raise ValueError(f"{name}: a cube needs a plane axis in front of the pixel axes")
+        return [x[i] for i in range(x.shape[0])]
+    return list(x)
+
+
+def _byte_ranges(planes):
+    import numpy as np
+    start = np.array([p.data_ptr() for p in planes], dtype=np.uint64)
+    return start, start + np.array([p.numel() * p.element_size() for p in planes], dtype=np.uint64)
+
+
+def mix_planes(inputs, weights, outputs=None, check_nan=False, stream=None):
+    """out[k] = sum_c weights[k, c] * inputs[c] over a stack of image planes:
+    every output element starts from +0.0 and adds its terms in ascending c,
+    the product and the sum each rounded once in float64 (numpy's
+    ``out[k] += inputs[c] * w``, bit for bit).
+
+    ``inputs`` and ``outputs`` are cubes (planes along the first axis) or
+    lists of device tensors, which may be separately allocated or slices of a
+    cube; every plane is contiguous and they all hold the same number of
+    elements.  The inputs are all float32 or all float64, the outputs
+    float64; without ``outputs`` a float64 cube [nout, *inputs[0].shape] is
+    allocated.  ``weights`` is a host array [nout, nin].  No output may
+    overlap an input or another output.  ``stream`` (a torch stream or a raw
+    handle) defaults to torch's current stream.
+
+    Returns the outputs; with ``check_nan`` the call waits for the stream and
+    returns (outputs, flags), flags the sum of MIX_NAN_INPUT (a NaN was read)
+    and MIX_NAN_OUTPUT (a NaN was written), 0 on clean data."""
+    import numpy as np
+    ins = _plane_list(inputs, "inputs")
+    if not ins:
+        raise ValueError("mix_planes needs at least one input plane")
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.ndim != 2 or w.shape[1] != len(ins) or w.shape[0] < 1:
+        raise ValueError(f"weights must be [nout, nin = {len(ins)}], not {w.shape}")
+    nout, nin = w.shape
+    if max(nin, nout) > MIX_PLANES_MAX:
+        raise ValueError(f"mix_planes takes at most {MIX_PLANES_MAX} input and as many output "
+                         f"planes, not {nin} and {nout}")
+    first = _on_gpu(ins[0], "inputs")
+    dev, npix = first.device, first.numel()
+    if first.dtype not in (torch.float32, torch.float64) or npix < 1:
+        raise ValueError("the input planes must be non-empty float32 or float64 tensors")
+    for p in ins:
+        _on_gpu(p, "inputs")
+        if p.dtype != first.dtype or p.device != dev or p.numel() != npix:
+            raise ValueError("the input planes must agree in dtype, device and size")
+        if not p.is_contiguous():
+            raise ValueError("every input plane must be contiguous")
+    result = outputs
+    if outputs is None:
+        result = outputs = _alloc((nout,) + tuple(first.shape), torch.float64, dev)
+    outs = _plane_list(outputs, "outputs")
+    if len(outs) != nout:
+        raise ValueError(f"{len(outs)} output planes for {nout} rows of weights")
+    for p in outs:
+        _on_gpu(p, "outputs")
+        if p.dtype != torch.float64 or p.device != dev or p.numel() != npix:
+            raise ValueError("the output planes must be float64 on the inputs' device and of "
+                             "their size")
+        if not p.is_contiguous():
+            raise ValueError("every output plane must be contiguous")
+    i_lo, i_hi = _byte_ranges(ins)
+    o_lo, o_hi = _byte_ranges(outs)
+    if ((o_lo[:, None] < i_hi[None, :]) & (i_lo[None, :] < o_hi[:, None])).any():
+        raise ValueError("an output plane overlaps an input plane")
+    order = np.argsort(o_lo)
+    if (o_hi[order][:-1] > o_lo[order][1:]).any():
+        raise ValueError("two output planes overlap")
+    in_tab = (ctypes.c_void_p * nin)(*[p.data_ptr() for p in ins])
+    out_tab = (ctypes.c_void_p * nout)(*[p.data_ptr() for p in outs])
+    if stream is None:
+        st = _stream(dev)
+    else:
+        st = ctypes.c_void_p(getattr(stream, "cuda_stream", stream))
+    seen = ctypes.c_int(0)
+    with torch.cuda.device(dev):
+        _lib.call("sdp_hip_mix_planes", nin, nout, npix, ctypes.cast(in_tab, ctypes.c_void_p),
+                  _DT_CODE[first.dtype], ctypes.cast(out_tab, ctypes.c_void_p),
+                  ctypes.c_void_p(w.ctypes.data),
+                  ctypes.byref(seen) if check_nan else ctypes.POINTER(ctypes.c_int)(), st)
+    return (result, seen.value) if check_nan else result
