@@ -866,6 +866,50 @@ int sdp_hip_mix_planes(int nin, int nout, int64_t npix,
                        int *nan_seen, void *stream, char *errbuf,
                        size_t errbuf_len);
 
+/* ---- gather of image facets (image/gather_scatter.py) ----------------------
+ * sdp_hip_gather_facets: an image [nplanes][ny][nx] from facets x facets
+ * sub-images [nplanes][dy][dx], facet (fy, fx) with its first pixel at
+ * (y0 + fy * sy, x0 + fx * sx) of the image (the raster of the reference's
+ * image_raster_iter: sy = dy - 2 * overlap, facets in fy-major order), which
+ * overlap where a step is smaller than the facet.  One pass: every facet pixel
+ * is read once, every output pixel written once.
+ *
+ * dtype (SDP_HIP_F32 or SDP_HIP_F64) is the type T of the facets and of both
+ * outputs.  facet_ptrs is a HOST table of facets^2 DEVICE pointers to the first
+ * element of each facet, plane_strides and row_strides host tables of the
+ * distance in elements between two planes and between two rows of each facet;
+ * the x stride is 1.  A facet may be a view of a larger image.  taper_y[dy] and
+ * taper_x[dx] are host fp64 arrays, or both NULL for weights of 1.  The library
+ * copies the tables to device scratch; they may be freed when the call returns.
+ * out and sumwt are contiguous device arrays [nplanes][ny][nx] that overlap no
+ * facet; either may be NULL, and with out == NULL no facet is read and the three
+ * facet tables may be NULL.  The call only enqueues work on `stream`.
+ *
+ * Per output element, over the facets that cover it in ascending fy, then
+ * ascending fx, each operation rounded once in T (no fused multiply-add):
+ *   acc = +0, sum = +0
+ *   wt  = (T)(taper_y[j] * taper_x[i])      the product in fp64
+ *   acc = acc + wt * v;  sum = sum + wt     (no tapers: acc = acc + v, wt = 1)
+ *   normalise != 0:  out = sum > 0 ? acc / sum : 0;  sumwt = sum
+ *   normalise == 0:  out = acc;                       sumwt = 1
+ * which is the reference's image_gather_facets with overlap > 0 and with
+ * overlap == 0, bit for bit (a -0.0 input gives +0.0; an uncovered pixel
+ * gives +0).
+ *
+ * 1 <= facets <= SDP_HIP_GATHER_FACETS_MAX per axis; 1 <= dy <= ny and
+ * 1 <= dx <= nx, at most 2^30 per side and 2^40 elements in all; sy, sx >= 1;
+ * y0, x0 >= 0 and the last facet ends inside the image; strides >= 0.
+ */
+#define SDP_HIP_GATHER_FACETS_MAX 256
+int sdp_hip_gather_facets(int dtype, int facets, int nplanes, int ny, int nx,
+                          int dy, int dx, int y0, int x0, int sy, int sx,
+                          const void *const *facet_ptrs,
+                          const int64_t *plane_strides,
+                          const int64_t *row_strides, const double *taper_y,
+                          const double *taper_x, int normalise, void *out,
+                          void *sumwt, void *stream, char *errbuf,
+                          size_t errbuf_len);
+
 #ifdef __cplusplus
 }
 #endif

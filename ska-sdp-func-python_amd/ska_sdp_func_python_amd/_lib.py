@@ -47,6 +47,7 @@ SDP_HIP_MIX_PLANES_REGS = 8
 SDP_HIP_MIX_PLANES_MAX = 4096
 SDP_HIP_MIX_NAN_INPUT = 1
 SDP_HIP_MIX_NAN_OUTPUT = 2
+SDP_HIP_GATHER_FACETS_MAX = 256
 
 c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
@@ -243,6 +244,11 @@ SIGNATURES = {
     "sdp_hip_mix_planes": [
         c_int, c_int, c_i64, c_vp, c_int,         # nin, nout, npix, in_planes (host), dtype
         c_vp, c_vp, ctypes.POINTER(c_int), c_vp] + _ERR,  # out_planes, weights (host), nan_seen, stream
+    "sdp_hip_gather_facets": [
+        c_int, c_int, c_int, c_int, c_int,        # dtype, facets, nplanes, ny, nx
+        c_int, c_int, c_int, c_int, c_int, c_int,  # dy, dx, y0, x0, sy, sx
+        c_vp, c_vp, c_vp, c_vp, c_vp, c_int,      # facet tables, tapers (host), normalise
+        c_vp, c_vp, c_vp] + _ERR,                 # out, sumwt, stream
 }
 
 _lock = threading.Lock()

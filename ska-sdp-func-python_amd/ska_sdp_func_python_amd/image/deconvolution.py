@@ -24,6 +24,7 @@ import torch
 from .. import _device
 from ..datamodels import Image
 from .cleaners import hogbom, msclean, msmfsclean
+from .gather_scatter import image_gather_channels, image_scatter_channels
 from .operations import convert_clean_beam_to_degrees, convert_clean_beam_to_pixels
 from .taylor_terms import (calculate_image_list_frequency_moments,
                            calculate_image_list_from_frequency_taylor_terms)
@@ -55,27 +56,12 @@ def _image_like(data, im):
 
 def _scatter_channels(im):
     """One single-channel Image per channel (None stays None)."""
-    if im is None:
-        return None
-    out = []
-    for chan in range(_pixels(im).shape[0]):
-        wcs = im.image_acc.wcs.deepcopy()
-        wcs.wcs.crval[3] += chan * wcs.wcs.cdelt[3]
-        sub = Image.constructor(data=_pixels(im)[chan:chan + 1],
-                                polarisation_frame=im.image_acc.polarisation_frame, wcs=wcs)
-        out.append(sub)
-    return out
+    return image_scatter_channels(im)
 
 
 def _gather_channels(image_list):
     """Concatenate single-channel Images along frequency."""
-    planes = [_pixels(im) for im in image_list]
-    data = torch.cat(planes) if isinstance(planes[0], torch.Tensor) else numpy.concatenate(planes)
-    out = _image_like(data, image_list[0])
-    for key, value in image_list[0].attrs.items():
-        if key not in out.attrs or out.attrs[key] is None:
-            out.attrs[key] = value
-    return out
+    return image_gather_channels(image_list)
 
 
 def deconvolve_list(dirty_list, psf_list, sensitivity_list=None, prefix="", **kwargs):
