@@ -910,6 +910,66 @@ int sdp_hip_gather_facets(int dtype, int facets, int nplanes, int ny, int nx,
                           void *sumwt, void *stream, char *errbuf,
                           size_t errbuf_len);
 
+/* ---- image segmentation (find_skycomponents) ---------------------------------
+ * The device half of find_skycomponents (reference src/ska_sdp_func_python/
+ * sky_component/operations.py:256-363, through photutils 1.8.0 detect_sources
+ * and SourceCatalog and astropy 5.2.2 convolve).  `planes` are nchan (nplanes)
+ * device planes [ny][nx], f32 or f64 (dtype), plane c at planes + c *
+ * plane_stride elements (Stokes I of a cube [nchan][npol][ny][nx]: stride npol
+ * * ny * nx); ny * nx < 2^31.  Every other array is a contiguous device array
+ * [ny][nx] of int32 unless said otherwise.  The calls only enqueue work.
+ *
+ * sdp_hip_segment_label: per pixel
+ *   mean   = (plane_0 + plane_1 + ... in channel order) / nchan, in the planes'
+ *            type (numpy.sum(axis=0) / float(nchan));
+ *   smooth = (sum over the ksize x ksize window centred on the pixel, rows then
+ *            columns, of mean * taps[dy][dx], fp64, a product and an add each
+ *            rounded once, pixels off the image 0) / tap_sum;
+ *   mask   = smooth > threshold
+ * and the 8-connected components of the mask.  taps is a HOST array [ksize]
+ * [ksize], ksize odd and at most SDP_HIP_SEGMENT_KERNEL_MAX; ksize 1 with tap
+ * 1 and tap_sum 1 is the identity.  labels[p] receives the flat index y * nx +
+ * x of the first pixel, in raster order, of the component of pixel p, or -1
+ * off the mask; count[r] of such a first pixel r its component's number of
+ * pixels (count elsewhere is not meaningful).  *nonfinite (device int32, to
+ * be zeroed by the caller) is set to 1 if a mean was not finite.  The result
+ * depends on the input alone, not on the schedule.
+ *
+ * sdp_hip_segment_roots: keep[p] = 1 where p is the first pixel of a component
+ * of at least npixels pixels, else 0.
+ *
+ * sdp_hip_segment_relabel: with rank the inclusive prefix sum of keep, the
+ * segment map: segmap[p] = rank[labels[p]] where keep[labels[p]], else 0 --
+ * the kept components numbered 1..n by their first pixel, which is the order
+ * of scipy.ndimage.label.  segmap may be labels.
+ *
+ * sdp_hip_segment_peaks: per plane c and segment s in 1..nseg the maximum of
+ * the plane over the pixels with segmap == s, values[c][s - 1] (f64; -0.0
+ * counts and is returned as +0.0), and the smallest flat index of a pixel
+ * that has it, indices[c][s - 1] (int64) -- photutils' max_value and
+ * maxval_index.  Integer atomics only: exact and repeatable.  A segment
+ * without a pixel gets 0 and -1.  The planes must be free of NaN.
+ */
+#define SDP_HIP_SEGMENT_TILE 32
+#define SDP_HIP_SEGMENT_KERNEL_MAX 15
+int sdp_hip_segment_label(int nchan, int ny, int nx, const void *planes,
+                          int dtype, int64_t plane_stride, int ksize,
+                          const double *taps, double tap_sum, double threshold,
+                          int32_t *labels, int32_t *count, int32_t *nonfinite,
+                          void *stream, char *errbuf, size_t errbuf_len);
+int sdp_hip_segment_roots(int ny, int nx, const int32_t *labels,
+                          const int32_t *count, int npixels, int32_t *keep,
+                          void *stream, char *errbuf, size_t errbuf_len);
+int sdp_hip_segment_relabel(int ny, int nx, const int32_t *labels,
+                            const int32_t *keep, const int32_t *rank,
+                            int32_t *segmap, void *stream, char *errbuf,
+                            size_t errbuf_len);
+int sdp_hip_segment_peaks(int nplanes, int ny, int nx, const void *planes,
+                          int dtype, int64_t plane_stride,
+                          const int32_t *segmap, int nseg, double *values,
+                          int64_t *indices, void *stream, char *errbuf,
+                          size_t errbuf_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,6 +48,8 @@ SDP_HIP_MIX_PLANES_MAX = 4096
 SDP_HIP_MIX_NAN_INPUT = 1
 SDP_HIP_MIX_NAN_OUTPUT = 2
 SDP_HIP_GATHER_FACETS_MAX = 256
+SDP_HIP_SEGMENT_TILE = 32
+SDP_HIP_SEGMENT_KERNEL_MAX = 15
 
 c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
@@ -249,6 +251,17 @@ SIGNATURES = {
         c_int, c_int, c_int, c_int, c_int, c_int,  # dy, dx, y0, x0, sy, sx
         c_vp, c_vp, c_vp, c_vp, c_vp, c_int,      # facet tables, tapers (host), normalise
         c_vp, c_vp, c_vp] + _ERR,                 # out, sumwt, stream
+    "sdp_hip_segment_label": [
+        c_int, c_int, c_int, c_vp, c_int, c_i64,  # nchan, ny, nx, planes, dtype, plane stride
+        c_int, c_vp, c_dbl, c_dbl,                # ksize, taps (host), tap_sum, threshold
+        c_vp, c_vp, c_vp, c_vp] + _ERR,           # labels, count, nonfinite, stream
+    "sdp_hip_segment_roots": [
+        c_int, c_int, c_vp, c_vp, c_int, c_vp, c_vp] + _ERR,  # ny, nx, labels, count, npixels, keep
+    "sdp_hip_segment_relabel": [
+        c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp] + _ERR,  # ny, nx, labels, keep, rank, segmap
+    "sdp_hip_segment_peaks": [
+        c_int, c_int, c_int, c_vp, c_int, c_i64,  # nplanes, ny, nx, planes, dtype, plane stride
+        c_vp, c_int, c_vp, c_vp, c_vp] + _ERR,    # segmap, nseg, values, indices, stream
 }
 
 _lock = threading.Lock()

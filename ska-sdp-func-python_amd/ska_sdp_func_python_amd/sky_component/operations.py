@@ -14,6 +14,13 @@ per image channel, the interpolation taps -- with the reference's arithmetic,
 and the pixels are updated by csrc/skycomp.hip.  An image whose pixels are a
 device tensor is updated in place and stays on the device; numpy pixels go
 through the device and are updated in place too.
+
+find_skycomponents (:256-363) turns an image back into components: channel
+mean, smoothing, 8-connected segmentation and the per-channel peak search run
+on the device (csrc/segment.hip), the O(segments x channels) rest on the host.
+segment_image returns its segment map.  The catalogue helpers that follow a
+find (:65-253, :565-580, :919-943) are small host functions; astropy's
+catalogue matching is replaced by SkyCoord.separation.
 """
 
 import collections.abc
@@ -24,12 +31,17 @@ import numpy as np
 from scipy import interpolate
 
 from .. import _device, kernels
-from ..datamodels import Image, SkyComponent, skycoord_to_pixel
+from ..datamodels import Image, SkyComponent, SkyCoord, pixel_to_skycoord, skycoord_to_pixel
 from ..image.operations import convert_clean_beam_to_pixels
 
 __all__ = ["apply_beam_to_skycomponent", "insert_skycomponent", "restore_skycomponent",
            "voronoi_decomposition", "image_voronoi_iter", "insert_function_sinc",
-           "insert_function_L", "insert_function_pswf", "grdsf"]
+           "insert_function_L", "insert_function_pswf", "grdsf", "find_skycomponents",
+           "segment_image", "segment_kernel", "find_nearest_skycomponent_index",
+           "find_nearest_skycomponent", "find_separation_skycomponents",
+           "find_skycomponent_matches_atomic", "find_skycomponent_matches",
+           "select_components_by_separation", "remove_neighbouring_components",
+           "filter_skycomponents_by_flux", "fit_skycomponent_spectral_index"]
 
 log = logging.getLogger("func-python-logger")
 
@@ -379,3 +391,226 @@ def image_voronoi_iter(im, components):
             mask = np.zeros(shape)
             mask[:, :, (labels == region)] = 1.0
         yield image_of(mask)
+
+
+# ---- find_skycomponents ----------------------------------------------------------
+def segment_kernel(fwhm):
+    """The smoothing kernel of find_skycomponents (:278-284): a Gaussian of the
+    given FWHM in pixels sampled at integer offsets on ``int(1.5 * fwhm)``
+    pixels a side, one more when that is even, normalised to unit sum."""
+    sigma = fwhm / (2.0 * np.sqrt(2.0 * np.log(2.0)))
+    size = int(1.5 * fwhm)
+    if size % 2 == 0:
+        size += 1
+    if size > kernels.SEGMENT_KERNEL_MAX:
+        raise ValueError(f"find_skycomponents: fwhm {fwhm} asks for a smoothing kernel of {size} "
+                         f"pixels a side; at most {kernels.SEGMENT_KERNEL_MAX} are supported")
+    if size == 1:
+        return np.ones((1, 1))
+    offsets = np.arange(size) - size // 2
+    r2 = offsets[:, None] ** 2 + offsets[None, :] ** 2
+    g = np.exp(-r2 / (2.0 * sigma ** 2))
+    return g / g.sum()
+
+
+def _segments(im, fwhm, threshold, npixels, who):
+    """The image's pixels on the device, their Stokes-I planes [nchan, ny, nx],
+    the segment map and the number of segments."""
+    pixels = im["pixels"].data
+    _check_pixels(pixels, who)
+    kernel = segment_kernel(fwhm)
+    dev_pixels = pixels if _device.is_device(pixels) else _device.to_dev(pixels)
+    planes = dev_pixels[:, 0]
+    labels, nlabels = kernels.segment_image(planes, threshold, npixels, kernel)
+    return dev_pixels, planes, labels, nlabels
+
+
+def segment_image(im, fwhm=1.0, threshold=1.0, npixels=5):
+    """The segment map that find_skycomponents works from: int32 [ny, nx], the
+    pixels of segment k (component "Segment k - 1") marked k, the background 0;
+    on the image's device when its pixels are a device tensor, else numpy.  An
+    image without a segment gives a map of zeros.  Not in the reference.
+
+    :return: segment map, number of segments
+    """
+    pixels = im["pixels"].data
+    _, _, labels, nlabels = _segments(im, fwhm, threshold, npixels, "segment_image")
+    return _device.like_input(labels, pixels), nlabels
+
+
+def find_skycomponents(im, fwhm=1.0, threshold=1.0, npixels=5):
+    """Find the components of an Image above a threshold (reference :256-363).
+
+    The mean over the channels of Stokes I is smoothed by a Gaussian of FWHM
+    ``fwhm`` pixels and cut into the 8-connected segments of at least
+    ``npixels`` pixels above ``threshold`` (photutils' detect_sources).  Each
+    segment, in the order of its first pixel, becomes a point SkyComponent
+    "Segment k": per channel the brightest Stokes-I pixel of the unsmoothed
+    image is found (the first in raster order on ties); direction and pixel
+    position are the means over the channels weighted with the absolute peak
+    values, and the flux is that of the pixel nearest to the mean position
+    (numpy.round), for all channels and polarisations.
+
+    Mean, smoothing, labelling and peak search run on the device
+    (csrc/segment.hip); device pixels stay there, and only the per-channel
+    peaks and the components' fluxes come to the host.  Where this differs
+    from the reference: the pixels must be float32 or float64; a pixel that
+    is not finite raises ``ValueError`` (photutils masks it); a smoothing
+    kernel of more than 15 pixels a side (fwhm >= 10.67) raises ``ValueError``.
+    A segment whose peaks are 0 in every channel has, as in the reference, a
+    NaN direction; its flux is then taken at the first channel's peak.
+
+    :param im: Image; pixels float64 or float32, numpy or a device tensor
+    :param fwhm: full width at half maximum of the smoothing Gaussian, pixels
+    :param threshold: detection threshold on the smoothed mean image
+    :param npixels: number of connected pixels a segment needs
+    :return: list of SkyComponents, flux a numpy array [nchan, npol]
+    """
+    import torch
+    log.debug("find_skycomponents: Finding components in Image by segmentation")
+    dev_pixels, planes, labels, nlabels = _segments(im, fwhm, threshold, npixels,
+                                                    "find_skycomponents")
+    if nlabels == 0:
+        raise ValueError("find_skycomponents: Failed to find any components")
+    log.info("find_skycomponents: Identified %d segments", nlabels)
+    nx = int(dev_pixels.shape[3])
+    values, indices = kernels.segment_peaks(planes, labels, nlabels)
+    values, indices = values.cpu().numpy(), indices.cpu().numpy()
+    wcs = im.image_acc.wcs
+    directions, cols, rows = [], [], []
+    all_xs, all_ys = (indices % nx).astype(float), (indices // nx).astype(float)
+    world = {}  # peak pixel -> (ra, dec): the channels of a segment mostly share theirs
+    for segment in range(nlabels):
+        flux = values[:, segment]
+        xs, ys = all_xs[:, segment], all_ys[:, segment]
+        for pixel, x, y in zip(indices[:, segment].tolist(), xs, ys):
+            if pixel not in world:
+                c = pixel_to_skycoord(x, y, wcs, 0)
+                world[pixel] = (c.ra.rad, c.dec.rad)
+        ras = np.array([world[pixel][0] for pixel in indices[:, segment].tolist()])
+        decs = np.array([world[pixel][1] for pixel in indices[:, segment].tolist()])
+        aflux = np.abs(flux)
+        flux_sum = np.sum(aflux)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            ra = np.sum(aflux * ras) / flux_sum
+            dec = np.sum(aflux * decs) / flux_sum
+            x = np.sum(aflux * xs) / flux_sum
+            y = np.sum(aflux * ys) / flux_sum
+        if not (np.isfinite(x) and np.isfinite(y)):
+            x, y = xs[0], ys[0]
+        directions.append(SkyCoord(ra, dec))
+        cols.append(int(np.round(x)))
+        rows.append(int(np.round(y)))
+    at = lambda v: torch.as_tensor(v, dtype=torch.int64, device=dev_pixels.device)
+    point_flux = dev_pixels[:, :, at(rows), at(cols)].permute(2, 0, 1).cpu().numpy()
+    frequency = np.asarray(im.frequency.data)
+    return [SkyComponent(direction=directions[k], frequency=frequency, name=f"Segment {k}",
+                         flux=point_flux[k], shape="Point",
+                         polarisation_frame=im.image_acc.polarisation_frame, params={})
+            for k in range(nlabels)]
+
+
+# ---- catalogue helpers (:65-253, :565-580, :919-943) ----------------------------
+# astropy's catalogue matching is replaced by the separations themselves:
+# nearest is the smallest separation, the first on ties.
+def find_nearest_skycomponent_index(home, comps):
+    """The index in ``comps`` of the component nearest to the direction ``home``."""
+    if len(comps) == 0:
+        raise ValueError("find_nearest_skycomponent_index: Catalog is empty")
+    return int(np.argmin([c.direction.separation(home).rad for c in comps]))
+
+
+def find_nearest_skycomponent(home, comps):
+    """The component nearest to ``home`` and its separation in rad."""
+    best = comps[find_nearest_skycomponent_index(home, comps)]
+    return best, best.direction.separation(home).rad
+
+
+def find_separation_skycomponents(comps_test, comps_ref=None):
+    """The matrix of separations (rad) [ref, test] of two lists of components;
+    of ``comps_test`` with itself when ``comps_ref`` is None."""
+    if comps_ref is None:
+        ncomps = len(comps_test)
+        distances = np.zeros([ncomps, ncomps])
+        for i in range(ncomps):
+            for j in range(i + 1, ncomps):
+                distances[i, j] = comps_test[i].direction.separation(comps_test[j].direction).rad
+                distances[j, i] = distances[i, j]
+        return distances
+    separations = np.zeros([len(comps_ref), len(comps_test)])
+    for ref, comp_ref in enumerate(comps_ref):
+        for test, comp_test in enumerate(comps_test):
+            separations[ref, test] = comp_test.direction.separation(comp_ref.direction).rad
+    return separations
+
+
+def find_skycomponent_matches_atomic(comps_test, comps_ref, tol=1e-7):
+    """Match candidates to reference components, many to one allowed: the list
+    of (test index, nearest reference index, separation) with separation < tol."""
+    if len(comps_test) and len(comps_ref) == 0:
+        raise ValueError("find_skycomponent_matches: Catalog is empty")
+    separations = find_separation_skycomponents(comps_test, comps_ref)
+    matches = []
+    for test in range(len(comps_test)):
+        best = int(np.argmin(separations[:, test]))
+        best_sep = separations[best, test]
+        if best_sep < tol:
+            matches.append((test, best, best_sep))
+    return matches
+
+
+def find_skycomponent_matches(comps_test, comps_ref, tol=1e-7):
+    """As find_skycomponent_matches_atomic (the reference's faster variant by
+    astropy's catalogue matching; here they are one)."""
+    return find_skycomponent_matches_atomic(comps_test, comps_ref, tol)
+
+
+def select_components_by_separation(home, comps, rmax=2 * np.pi, rmin=0.0):
+    """The components whose separation from ``home`` lies in [rmin, rmax] rad."""
+    return [comp for comp in comps if rmin <= comp.direction.separation(home).rad <= rmax]
+
+
+def remove_neighbouring_components(comps, distance):
+    """Of two components closer than ``distance`` rad, drop the fainter (by its
+    largest flux), pairs taken in list order as in the reference (:228-253).
+
+    :return: indices of the components kept, the components kept
+    """
+    ncomps = len(comps)
+    ok = ncomps * [True]
+    for i in range(ncomps):
+        if ok[i]:
+            for j in range(i + 1, ncomps):
+                if ok[j]:
+                    d = comps[i].direction.separation(comps[j].direction).rad
+                    if d < distance:
+                        if np.max(comps[i].flux) > np.max(comps[j].flux):
+                            ok[j] = False
+                        else:
+                            ok[i] = False
+                        break
+    idx = [i for i in range(ncomps) if ok[i]]
+    return idx, [comps[i] for i in idx]
+
+
+def filter_skycomponents_by_flux(sc, flux_min=-np.inf, flux_max=np.inf):
+    """The components whose largest Stokes-I flux lies strictly between the limits."""
+    return [comp for comp in sc if flux_min < np.max(comp.flux[:, 0]) < flux_max]
+
+
+def fit_skycomponent_spectral_index(sc):
+    """The spectral index of a multi-frequency component: the slope of log10
+    flux (Stokes I) against log10 frequency, both relative to the centre
+    channel; 0.0 for a single channel or a centre that is not positive."""
+    frequency = np.asarray(sc.frequency, dtype=float)
+    nchan = frequency.shape[0]
+    if nchan <= 1:
+        log.warning("Single frequency skycomponent, skip fitting")
+        return 0.0
+    centre = nchan // 2
+    if frequency[centre] > 0.0 and sc.flux[centre, 0] > 0.0:
+        xdata = np.log10(frequency / frequency[centre])
+        ydata = np.log10(sc.flux[:, 0] / sc.flux[centre, 0])
+        return np.polyfit(xdata, ydata, 1)[0]
+    log.warning("Wrong values encountered, no fitting performed.")
+    return 0.0
