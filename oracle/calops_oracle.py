@@ -16,6 +16,10 @@ ska-sdp-func-python_amd/csrc/calops.hip.
   divide_visibility's point-source visibilities
   (src/ska_sdp_func_python/visibility/operations.py:145-189)
 
+* solve_gaintable_fixture   solve_gaintable (solvers.py:21-145) composed of
+  point_sums, ref_oracle.stefcal_row and the row rules around them, on the
+  tests/golden/solve_ragged_*.npz fixtures
+
 Pinned by tests/golden/applygt_*.npz (the reference's apply_gaintable run by
 tests/golden/make_golden.py) and, for point_sums, by the solve_*.npz
 fixtures through the reference's solve_gaintable.
@@ -139,3 +143,34 @@ def point_sums(vis, weight, flags, time, gt_time, gt_interval, nchan_g, model=No
         xb[r] = a if nchan_g > 1 else a[:, None, :]
         xwtb[r] = b if nchan_g > 1 else b[:, None, :]
     return xb, xwtb
+
+
+def solve_gaintable_fixture(g, vis=None, model=None):
+    """solve_gaintable (solvers.py:21-145) restated on a tests/golden/
+    solve_ragged_*.npz fixture ``g`` (weights, flags, autocorrelations,
+    reversed baselines, a gain row without weight and one without times):
+    point_sums, ref_oracle.stefcal_row per row, gain 1 / weight 0 /
+    residual 0 for a row without weight (:130-133), the input kept for a row
+    whose window holds no time (:93-97), then the table-wide mean / median
+    normalisation (:135-143).  ``vis`` / ``model`` replace the fixture's (the
+    complex64-rounded ones).  Returns (gain, weight, residual)."""
+    import ref_oracle as ro
+    nants, nchan_g = g["gain_in"].shape[1:3]
+    time, gt_time, half = g["time"], g["gt_time"], g["gt_interval"] / 2
+    xb, xwt = point_sums(g["vis"] if vis is None else vis, g["vis_weight"],
+                         g["vis_flags"].astype(int), time, gt_time, g["gt_interval"], nchan_g,
+                         model=g["model"] if model is None else model)
+    gain, gwt, res = g["gain_in"].copy(), g["weight_in"].copy(), g["residual_in"].copy()
+    for row, t in enumerate(gt_time):
+        if not np.any((time >= t - half[row]) & (time <= t + half[row])):
+            continue
+        if not np.any(xwt[row] > 0):
+            gain[row], gwt[row], res[row] = 1.0, 0.0, 0.0
+            continue
+        gain[row], gwt[row], res[row], _ = ro.stefcal_row(
+            xb[row], xwt[row], g["baselines"], nants, g["gain_in"][row], g["weight_in"][row],
+            int(g["niter"]), float(g["tol"]), bool(g["phase_only"]), bool(g["crosspol"]))
+    norm = str(g["normalise"])
+    if norm in ("mean", "median") and not bool(g["phase_only"]):
+        gain = gain / (np.mean if norm == "mean" else np.median)(np.abs(gain))
+    return gain, gwt, res

@@ -12,7 +12,10 @@ Mirrors reference ``src/ska_sdp_func_python/calibration/solvers.py``:
 * the inner solvers (:148-539) run batched over all rows in one call of
   ``sdp_hip_solve_gains``: scalar (npol 1), matrix (npol 4 with crosspol)
   and "nocrossdata" (npol 2, or 4 without crosspol), with the reference's
-  channel-coupled convergence, damping 0.5 and refant 0.
+  channel-coupled convergence, damping 0.5 and refant 0.  The solver sees
+  the cross-correlations only; the reference's row maximum (:167) also runs
+  over the autocorrelations, so the gain weights are rescaled by
+  max(cross) / max(all) afterwards.
 
 The point-source sums (:99-107) are formed on the device; the reference's
 dense [nants, nants] matrix (:108-114) is replaced by a canonical packed
@@ -152,6 +155,16 @@ def solve_gaintable(vis, modelvis=None, gain_table=None, phase_only=True, niter=
     if r1 > r0:
         residual, used = kernels.solve_gains(xb_c, xwt_c, gain, gwt, row_start, ant2, mode,
                                              niter=niter, tol=tol, phase_only=phase_only)
+        if len(autos) and nc > 0 and niter > 0:
+            # the reference takes the row maximum that normalises the weights
+            # over the dense matrix with its diagonal (solvers.py:116, :167)
+            # and zeroes the diagonal afterwards (:251-253); the solver saw
+            # the cross-correlations only.  Gains and residuals do not depend
+            # on the scale of the weights, the gain weights are linear in it.
+            mx_all = xwt.reshape(xwt.shape[0], -1).amax(dim=1)
+            mx_c = xwt_c.reshape(xwt_c.shape[0], -1).amax(dim=1)
+            scale = torch.where(mx_all > 0, mx_c / mx_all.clamp_min(1e-300), torch.ones_like(mx_c))
+            gwt = gwt * scale[:, None, None, None, None]
     else:
         residual = torch.zeros(res_h.shape, dtype=torch.float64, device=dev)
         used = torch.zeros(0, dtype=torch.int32, device=dev)

@@ -13,7 +13,11 @@ inputs and outputs are stored -- no reference source text.
 Fixtures:
   dft_*.npz        dft_cpu_looped                (imaging/dft.py:265-285)
   solve_*.npz      solve_gaintable end-to-end    (calibration/solvers.py:21-539,
-                   with visibility/operations.py:145-189 divide_visibility)
+                   with visibility/operations.py:145-189 divide_visibility);
+                   solve_ragged_*.npz: the same on tables with autocorrelations,
+                   reversed baselines, weights, flags, an empty and an absent
+                   gain row; solve_scalar_direct_refant.npz: the scalar solver
+                   (:217-284) called with refant 4, damping 0.3
   cfgrid_*.npz     grid_visibility_to_griddata / degrid_visibility_from_griddata
                    with spatial_mapping         (grid_data/gridding.py:33-255, :502-590)
   fft_*.npz        fft / ifft centred transforms (fourier_transforms/fft_support.py:31-140)
@@ -166,6 +170,170 @@ def make_solver():
     }
     for k, (pf, na, nt, nc, jones, po, cp, norm, amp) in cases.items():
         save(f"solve_{k}.npz", **_solver_case(pf, na, nt, nc, jones, po, cp, norm, amp, seed=len(k)))
+    make_solver_ragged()
+
+
+def make_solver_ragged():
+    for k, kw in RAGGED_CASES.items():
+        save(f"solve_{k}.npz", **_solver_case_ragged(**kw))
+    save("solve_scalar_direct_refant.npz", **_solver_case_direct())
+
+
+# solve_gaintable on what an observation's table looks like rather than a tidy
+# simulation: see _solver_case_ragged.  Two column blocks of the device solver
+# (65-67 antennas) in every case.
+RAGGED_CASES = {
+    "ragged_scalar_T_median": dict(pf="stokesI", nants=65, ntimes=3, nchan=2, jones="T",
+                                   phase_only=False, crosspol=False, normalise="median",
+                                   amp_err=0.1, seed=101, auto_spike=True),
+    "ragged_matrix_B": dict(pf="linear", nants=66, ntimes=2, nchan=1, jones="B",
+                            phase_only=False, crosspol=True, normalise="mean", amp_err=0.05,
+                            seed=112),
+    "ragged_nocross_T": dict(pf="linear", nants=67, ntimes=2, nchan=1, jones="T",
+                             phase_only=True, crosspol=False, normalise=None, amp_err=0.0,
+                             seed=103, cross_scale=2.0),
+}
+
+
+def _solver_case_ragged(pf, nants, ntimes, nchan, jones, phase_only, crosspol, normalise, amp_err,
+                        seed, niter=200, tol=1e-6, auto_spike=False, cross_scale=0.1):
+    """The reference's solve_gaintable on: autocorrelations among the
+    baselines, baselines in shuffled order with half of them given as
+    (a2, a1), weights in [0.5, 2], 5 % flags, time 1 wholly flagged (a gain row
+    without weight: gain 1 / weight 0 / residual 0, solvers.py:130-133), a
+    starting table that is not all ones, and a last gain row whose window holds
+    no visibility time (kept as given, :93-97).  ``auto_spike`` gives one
+    autocorrelation the largest weight of row 0: the reference's row maximum
+    (:167) runs over the dense matrix, diagonal included.  ``cross_scale`` is
+    the model amplitude of the cross hands relative to the parallel ones; at 2
+    the largest point-source weight of every row lies in a cross hand."""
+    import calops_oracle as co
+    import ref_oracle as ro
+    rng = np.random.default_rng(seed)
+    p = dm.PolarisationFrame(pf)
+    npol = p.npol
+    i, j = np.triu_indices(nants, 0)            # autocorrelations included
+    order = rng.permutation(i.size)
+    i, j = i[order], j[order]
+    swap = rng.uniform(size=i.size) < 0.5
+    bl = np.stack([np.where(swap, j, i), np.where(swap, i, j)], 1)
+    nbl = len(bl)
+    shape = (ntimes, nbl, nchan, npol)
+    times = 100.0 + 10.0 * np.arange(ntimes)
+    model = rng.normal(1.0, 0.2, shape) * np.exp(1j * rng.uniform(-np.pi, np.pi, shape))
+    if npol == 4:
+        model[..., 1:3] *= cross_scale
+    nrec = 1 if npol == 1 else 2
+    gchan = nchan if jones == "B" else 1
+    phases = rng.normal(0, 0.3, (ntimes, nants, gchan, nrec, nrec))
+    amps = rng.lognormal(0, amp_err, phases.shape) if amp_err > 0 else 1.0
+    g = amps * np.exp(1j * phases)
+    if nrec == 2:
+        g[..., 0, 1] = g[..., 1, 0] = 0.0
+    obs = np.zeros(shape, complex)
+    for f in range(nchan):
+        g1 = g[:, bl[:, 0], min(f, gchan - 1)]      # [t, bl, nrec, nrec]
+        g2 = g[:, bl[:, 1], min(f, gchan - 1)]
+        if npol == 1:
+            obs[:, :, f, 0] = g1[..., 0, 0] * model[:, :, f, 0] * np.conj(g2[..., 0, 0])
+        else:
+            obs[:, :, f] = np.einsum("tbij,tbjk,tblk->tbil", g1, model[:, :, f].reshape(
+                ntimes, nbl, 2, 2), np.conj(g2)).reshape(ntimes, nbl, 4)
+    obs += 1e-3 * (rng.normal(size=shape) + 1j * rng.normal(size=shape))
+    weight = rng.uniform(0.5, 2.0, shape)
+    flags = (rng.uniform(size=shape) < 0.05).astype(int)
+    flags[1] = 1
+    if auto_spike:
+        ia = int(np.nonzero(bl[:, 0] == bl[:, 1])[0][3])
+        weight[0, ia] = 50.0
+        flags[0, ia] = 0
+    vis = dm.Visibility.constructor(
+        frequency=np.linspace(1.0e8, 1.1e8, nchan), channel_bandwidth=np.full(nchan, 1e6),
+        phasecentre=dm.SkyCoord(0.0, -0.8), uvw=np.zeros((ntimes, nbl, 3)), time=times,
+        vis=obs, weight=weight, flags=flags, baselines=bl, polarisation_frame=p,
+        integration_time=np.full(ntimes, 10.0))
+    modelvis = vis.copy(deep=True)
+    modelvis["vis"].data = model
+    # the table: one row per time, one more far outside them
+    nrow = ntimes + 1
+    gshape = (nrow, nants, gchan, nrec, nrec)
+    gain_in = rng.uniform(0.9, 1.1, gshape) * np.exp(1j * rng.uniform(-0.2, 0.2, gshape))
+    weight_in = rng.uniform(0.5, 1.5, gshape)
+    residual_in = rng.uniform(0.1, 0.2, (nrow, gchan, nrec, nrec))
+    gain_in[-1] = (2.0 - 3.0j) * gain_in[-1]
+    weight_in[-1] += 7.0
+    residual_in[-1] += 0.25
+    gt_time = np.concatenate([times, [times[-1] + 1000.0]])
+    gt_interval = np.full(nrow, 10.0)
+    freq_g = vis.frequency.data if jones == "B" else np.array([np.mean(vis.frequency.data)])
+    rf = dm.PolarisationFrame("stokesI" if nrec == 1 else "linear")
+    gt_in = dm.GainTable.constructor(gain_in.copy(), gt_time, gt_interval, weight_in.copy(),
+                                     residual_in.copy(), freq_g, rf, vis.phasecentre, None, jones)
+    ns = _ref_solver_namespace()
+    gt = ns["solve_gaintable"](vis, modelvis, gain_table=gt_in.copy(deep=True),
+                               phase_only=phase_only, niter=niter, tol=tol, crosspol=crosspol,
+                               normalise_gains=normalise, jones_type=jones)
+    # what the case is meant to hold, checked on the point-source sums
+    xb, xwt = co.point_sums(obs, weight, flags, times, gt_time, gt_interval, gchan, model=model)
+    assert xwt[0].max() > 0 and xwt[1].max() == 0 and xwt[-1].max() == 0
+    auto = bl[:, 0] == bl[:, 1]
+    for row in np.nonzero(xwt.reshape(nrow, -1).max(1) > 0)[0]:
+        if auto_spike and row == 0:
+            assert xwt[row][auto].max() > 2 * xwt[row][~auto].max()
+        if npol == 4 and cross_scale > 1:
+            assert np.unravel_index(np.argmax(xwt[row]), xwt[row].shape)[-1] in (1, 2)
+        # no iteration's change within 5 % of tol: the stopping iteration of a
+        # solver that stores x in fp32 is then the reference's
+        ch = []
+        ro.stefcal_row(xb[row], xwt[row], bl, nants, gain_in[row], weight_in[row], niter, tol,
+                       phase_only, crosspol, changes=ch)
+        assert len(ch) < niter and not np.any(np.abs(np.array(ch) - tol) < 0.05 * tol), ch[-3:]
+    # the absent row comes back as given (its gain only divided by the
+    # table-wide mean / median amplitude of :135-143)
+    ratio = gt["gain"].data[-1] / gain_in[-1]
+    np.testing.assert_allclose(ratio, ratio.flat[0], rtol=1e-14)
+    np.testing.assert_array_equal(gt["weight"].data[-1], weight_in[-1])
+    np.testing.assert_array_equal(gt["residual"].data[-1], residual_in[-1])
+    return dict(vis=obs, model=model, vis_weight=weight, vis_flags=flags.astype(np.int8),
+                uvw=np.zeros((ntimes, nbl, 3)), time=times,
+                frequency=np.asarray(vis.frequency.data), baselines=bl,
+                integration_time=np.asarray(vis.integration_time.data),
+                pol_frame=np.array(pf), jones=np.array(jones), phase_only=np.array(phase_only),
+                crosspol=np.array(crosspol), normalise=np.array(str(normalise)),
+                niter=np.array(niter), tol=np.array(tol),
+                gain_in=gain_in, weight_in=weight_in, residual_in=residual_in,
+                gt_time=gt_time, gt_interval=gt_interval, gt_frequency=np.asarray(freq_g),
+                gain=gt["gain"].data, weight=gt["weight"].data, residual=gt["residual"].data)
+
+
+def _solver_case_direct(nants=11, nchan=2, refant=4, damping=0.3, niter=60, tol=1e-7, seed=104):
+    """_solve_antenna_gains_itsubs_scalar called directly with a reference
+    antenna other than 0 and a damping other than 0.5 (solvers.py:225-226),
+    on the dense x / xwt that solve_gaintable would hand it (:108-114,
+    :165-168) for the stored baseline sums."""
+    rng = np.random.default_rng(seed)
+    a1, a2 = np.triu_indices(nants, 1)
+    g = rng.uniform(0.8, 1.2, (nants, nchan)) * np.exp(1j * rng.normal(0, 0.5, (nants, nchan)))
+    xwt_b = rng.uniform(0.5, 2.0, (a1.size, nchan, 1))
+    x_b = (g[a1] * np.conj(g[a2]))[..., None] + 0.02 * (
+        rng.normal(size=xwt_b.shape) + 1j * rng.normal(size=xwt_b.shape))
+    x_b = x_b * xwt_b
+    x = np.zeros((nants, nants, nchan, 1), complex)
+    xwt = np.zeros((nants, nants, nchan, 1))
+    x[a1, a2], x[a2, a1] = np.conjugate(x_b), x_b
+    xwt[a1, a2] = xwt[a2, a1] = xwt_b
+    mask = xwt > 0
+    x[mask] = x[mask] / xwt[mask]
+    xwt[mask] = xwt[mask] / np.max(xwt[mask])
+    gain_in = rng.uniform(0.9, 1.1, (nants, nchan, 1, 1)) * np.exp(
+        1j * rng.uniform(-0.2, 0.2, (nants, nchan, 1, 1)))
+    ns = _ref_solver_namespace()
+    gain, gwt, res = ns["_solve_antenna_gains_itsubs_scalar"](
+        gain_in.copy(), np.ones(gain_in.shape), x.copy(), xwt.copy(), niter=niter, tol=tol,
+        phase_only=False, refant=refant, damping=damping)
+    return dict(x=x, xwt=xwt, x_b=x_b, xwt_b=xwt_b, baselines=np.stack([a1, a2], 1),
+                gain_in=gain_in, refant=np.array(refant), damping=np.array(damping),
+                niter=np.array(niter), tol=np.array(tol), gain=gain, weight=gwt, residual=res)
 
 
 # ---------------------------------------------------------------------------
