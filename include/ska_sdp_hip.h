@@ -555,6 +555,30 @@ int sdp_hip_apply_gains(int64_t ntimes, int nbl, int nchan, int npol,
                         const int32_t *time_row, const void *gain, int nrow_g,
                         int nants, int nchan_g, int nrec, int inverse,
                         void *stream, char *errbuf, size_t errbuf_len);
+/*
+ * sdp_hip_apply_gain_chain: the gain tables of apply_calibration_chain
+ * (calibration/chain_calibration.py:75-134) applied in the given order in ONE
+ * pass over vis / weight (in place), bit for bit what ntab calls of
+ * sdp_hip_apply_gains with use_flags = 0 give: an element stays in registers,
+ * and a complex64 value is rounded to float between two tables as a store
+ * and reload would round it; weights stay f64.  1 <= ntab <=
+ * SDP_HIP_GAIN_CHAIN_MAX (longer chains: consecutive calls).  gains and
+ * time_rows are HOST arrays of ntab device pointers: table k has gains c128
+ * [nrow_g[k], nants, nchan_g[k], nrec[k], nrec[k]] and its own time_row map
+ * [ntimes] (device int32, -1 = no row of table k owns this time); nrow_g,
+ * nchan_g, nrec are host int32 [ntab].  One inverse flag for the whole chain.
+ * An element whose time no table covers is not written.  Refused: ntab outside
+ * the range, nrec not 1 or 2, npol 2 or 4 with nrec 1, null pointers.
+ */
+#define SDP_HIP_GAIN_CHAIN_MAX 8
+int sdp_hip_apply_gain_chain(int64_t ntimes, int nbl, int nchan, int npol,
+                             void *vis, int vis_dtype, double *weight,
+                             const int32_t *ant1, const int32_t *ant2,
+                             int nants, int ntab, const void *const *gains,
+                             const int32_t *const *time_rows,
+                             const int32_t *nrow_g, const int32_t *nchan_g,
+                             const int32_t *nrec, int inverse, void *stream,
+                             char *errbuf, size_t errbuf_len);
 
 /*
  * Imaging weights, replacing the Python row loops of

@@ -5,6 +5,8 @@
 //                        written in StefCal's canonical baseline order
 //   sdp_hip_divide_vis   divide_visibility alone
 //   sdp_hip_apply_gains  apply_gaintable (calibration/operations.py:23-256)
+//   sdp_hip_apply_gain_chain  the tables of apply_calibration_chain
+//                        (calibration/chain_calibration.py:75-134) in one pass
 //
 // All visibility-shaped arrays are the Visibility's [ntimes, nbl, nchan, npol]
 // in C order.  Arithmetic follows the reference's fp64 operations: complex
@@ -232,6 +234,85 @@ __global__ __launch_bounds__(kThreads) void k_row_flagged(Shape s, const void *_
     }
 }
 
+// One gain table on one (time, baseline, channel) element: v / w are the
+// element's npol visibilities and weights, r its gain row, a1 / a2 the
+// baseline's antennas, lg / ok the effective gains of k_gain_prep.  The one
+// statement of apply_gaintable's arithmetic, shared by k_apply and
+// k_apply_chain: a gain channel acts on its own vis channel only
+// (f < nchan_g), npol 1 is the scalar Mueller product, npol 2 / 4 are
+// (G1 V) conj(G2) in numpy's order, and where no inverse exists vis and
+// weight are zeroed.
+__device__ __forceinline__ void apply_element(cplx *v, double *w, int npol, int f, int r, int a1,
+                                              int a2, const double2 *__restrict__ lg,
+                                              const uint8_t *__restrict__ ok, int nants,
+                                              int nchan_g, int nrec, int inverse) {
+    if (f >= nchan_g) return;
+    const int m = nrec * nrec;
+    const int64_t g1i = ((int64_t)r * nants + a1) * nchan_g + f;
+    const int64_t g2i = ((int64_t)r * nants + a2) * nchan_g + f;
+    const double2 *G1 = lg + g1i * m;
+    const double2 *G2 = lg + g2i * m;
+    if (npol == 1) {
+        // smueller = sum_{l,m} g1[l,m] conj(g2[l,m])  (einsum ijlm,kjlm->jik)
+        cplx sm = {0.0, 0.0};
+        for (int k = 0; k < m; ++k)
+            sm = cadd(sm, cmul({G1[k].x, G1[k].y}, cconj({G2[k].x, G2[k].y})));
+        if (hypot(sm.re, sm.im) > 0.0) {
+            v[0] = cmul(v[0], sm);
+        } else {
+            v[0] = {0.0, 0.0};
+            w[0] = 0.0;
+        }
+        return;
+    }
+    const bool good = !inverse || (ok[g1i] && ok[g2i]);
+    if (!good) {
+        if (npol == 2) {
+            v[0] = {0.0, 0.0};
+            w[0] = 0.0;
+        } else {
+            for (int p = 0; p < 4; ++p) {
+                v[p] = {0.0, 0.0};
+                w[p] = 0.0;
+            }
+        }
+        return;
+    }
+    const cplx g1[2][2] = {{{G1[0].x, G1[0].y}, {G1[1].x, G1[1].y}},
+                           {{G1[2].x, G1[2].y}, {G1[3].x, G1[3].y}}};
+    const cplx c2[2][2] = {{cconj({G2[0].x, G2[0].y}), cconj({G2[1].x, G2[1].y})},
+                           {cconj({G2[2].x, G2[2].y}), cconj({G2[3].x, G2[3].y})}};
+    cplx V[2][2];
+    if (npol == 2) {
+        V[0][0] = v[0];
+        V[0][1] = {0.0, 0.0};
+        V[1][0] = {0.0, 0.0};
+        V[1][1] = v[1];
+    } else {
+        V[0][0] = v[0];
+        V[0][1] = v[1];
+        V[1][0] = v[2];
+        V[1][1] = v[3];
+    }
+    // (G1 @ V) @ conj(G2), numpy's evaluation order
+    cplx T[2][2], R[2][2];
+    for (int i2 = 0; i2 < 2; ++i2)
+        for (int k2 = 0; k2 < 2; ++k2)
+            T[i2][k2] = cadd(cmul(g1[i2][0], V[0][k2]), cmul(g1[i2][1], V[1][k2]));
+    for (int i2 = 0; i2 < 2; ++i2)
+        for (int k2 = 0; k2 < 2; ++k2)
+            R[i2][k2] = cadd(cmul(T[i2][0], c2[0][k2]), cmul(T[i2][1], c2[1][k2]));
+    if (npol == 2) {
+        v[0] = R[0][0];
+        v[1] = R[1][1];
+    } else {
+        v[0] = R[0][0];
+        v[1] = R[0][1];
+        v[2] = R[1][0];
+        v[3] = R[1][1];
+    }
+}
+
 __global__ __launch_bounds__(kThreads) void k_apply(Shape s, void *vis, int c128, double *weight,
                                                     const void *__restrict__ flags, int fbytes,
                                                     const int32_t *__restrict__ ant1,
@@ -263,76 +344,144 @@ __global__ __launch_bounds__(kThreads) void k_apply(Shape s, void *vis, int c128
             w[p] *= k;
         }
     }
-    if (f < nchan_g) {
-        const int m = nrec * nrec;
-        const int64_t g1i = ((int64_t)r * nants + ant1[b]) * nchan_g + f;
-        const int64_t g2i = ((int64_t)r * nants + ant2[b]) * nchan_g + f;
-        const double2 *G1 = lg + g1i * m;
-        const double2 *G2 = lg + g2i * m;
-        if (s.npol == 1) {
-            // smueller = sum_{l,m} g1[l,m] conj(g2[l,m])  (einsum ijlm,kjlm->jik)
-            cplx sm = {0.0, 0.0};
-            for (int k = 0; k < m; ++k)
-                sm = cadd(sm, cmul({G1[k].x, G1[k].y}, cconj({G2[k].x, G2[k].y})));
-            if (hypot(sm.re, sm.im) > 0.0) {
-                v[0] = cmul(v[0], sm);
-            } else {
-                v[0] = {0.0, 0.0};
-                w[0] = 0.0;
-            }
-        } else {
-            const bool good = !inverse || (ok[g1i] && ok[g2i]);
-            const cplx g1[2][2] = {{{G1[0].x, G1[0].y}, {G1[1].x, G1[1].y}},
-                                   {{G1[2].x, G1[2].y}, {G1[3].x, G1[3].y}}};
-            const cplx c2[2][2] = {{cconj({G2[0].x, G2[0].y}), cconj({G2[1].x, G2[1].y})},
-                                   {cconj({G2[2].x, G2[2].y}), cconj({G2[3].x, G2[3].y})}};
-            if (!good) {
-                if (s.npol == 2) {
-                    v[0] = {0.0, 0.0};
-                    w[0] = 0.0;
-                } else {
-                    for (int p = 0; p < 4; ++p) {
-                        v[p] = {0.0, 0.0};
-                        w[p] = 0.0;
-                    }
-                }
-            } else {
-                cplx V[2][2];
-                if (s.npol == 2) {
-                    V[0][0] = v[0];
-                    V[0][1] = {0.0, 0.0};
-                    V[1][0] = {0.0, 0.0};
-                    V[1][1] = v[1];
-                } else {
-                    V[0][0] = v[0];
-                    V[0][1] = v[1];
-                    V[1][0] = v[2];
-                    V[1][1] = v[3];
-                }
-                // (G1 @ V) @ conj(G2), numpy's evaluation order
-                cplx T[2][2], R[2][2];
-                for (int i2 = 0; i2 < 2; ++i2)
-                    for (int k2 = 0; k2 < 2; ++k2)
-                        T[i2][k2] = cadd(cmul(g1[i2][0], V[0][k2]), cmul(g1[i2][1], V[1][k2]));
-                for (int i2 = 0; i2 < 2; ++i2)
-                    for (int k2 = 0; k2 < 2; ++k2)
-                        R[i2][k2] = cadd(cmul(T[i2][0], c2[0][k2]), cmul(T[i2][1], c2[1][k2]));
-                if (s.npol == 2) {
-                    v[0] = R[0][0];
-                    v[1] = R[1][1];
-                } else {
-                    v[0] = R[0][0];
-                    v[1] = R[0][1];
-                    v[2] = R[1][0];
-                    v[3] = R[1][1];
-                }
-            }
-        }
-    }
+    apply_element(v, w, s.npol, f, r, ant1[b], ant2[b], lg, ok, nants, nchan_g, nrec, inverse);
     for (int p = 0; p < s.npol; ++p) {
         store_c(vis, c128, base + p, v[p]);
         weight[base + p] = w[p];
     }
+}
+
+// ---- a chain of gain tables in one pass ------------------------------------
+// apply_calibration_chain applies its tables one after another; n calls of
+// k_apply read and write every visibility and weight n times.  Here an
+// element stays in registers while the tables act on it in order.  Between two
+// tables a complex64 value is rounded to float, as the store and reload of
+// consecutive k_apply launches round it, so the result is theirs bit for bit
+// (use_flags = 0).  An element that no table covers is not written.
+constexpr int kMaxChain = SDP_HIP_GAIN_CHAIN_MAX;
+
+struct ChainTable {
+    const double2 *lg;        // effective gains (k_gain_prep)
+    const uint8_t *ok;
+    const int32_t *time_row;  // [ntimes] gain row of each vis time or -1
+    int nrow_g, nchan_g, nrec;
+};
+
+struct Chain {
+    int ntab;
+    ChainTable t[kMaxChain];
+};
+
+// the npol values of one element; VEC: vis and weight are 16-byte aligned and
+// an element (npol >= 2) moves as 16-byte accesses
+template <int NPOL, bool C128, bool VEC>
+__device__ __forceinline__ void load_element(const void *vis, const double *weight, size_t base,
+                                             cplx *v, double *w) {
+    if constexpr (VEC && NPOL >= 2) {
+        if constexpr (C128) {
+            for (int p = 0; p < NPOL; ++p) v[p] = load_c(vis, 1, base + p);
+        } else {
+            const float4 *pv =
+                reinterpret_cast<const float4 *>(static_cast<const float2 *>(vis) + base);
+            for (int q = 0; q < NPOL / 2; ++q) {
+                const float4 x = pv[q];
+                v[2 * q] = {(double)x.x, (double)x.y};
+                v[2 * q + 1] = {(double)x.z, (double)x.w};
+            }
+        }
+        const double2 *pw = reinterpret_cast<const double2 *>(weight + base);
+        for (int q = 0; q < NPOL / 2; ++q) {
+            const double2 x = pw[q];
+            w[2 * q] = x.x;
+            w[2 * q + 1] = x.y;
+        }
+    } else {
+        for (int p = 0; p < NPOL; ++p) {
+            v[p] = load_c(vis, C128, base + p);
+            w[p] = weight[base + p];
+        }
+    }
+}
+
+template <int NPOL, bool C128, bool VEC>
+__device__ __forceinline__ void store_element(void *vis, double *weight, size_t base,
+                                              const cplx *v, const double *w) {
+    if constexpr (VEC && NPOL >= 2) {
+        if constexpr (C128) {
+            for (int p = 0; p < NPOL; ++p) store_c(vis, 1, base + p, v[p]);
+        } else {
+            float4 *pv = reinterpret_cast<float4 *>(static_cast<float2 *>(vis) + base);
+            for (int q = 0; q < NPOL / 2; ++q)
+                pv[q] = make_float4((float)v[2 * q].re, (float)v[2 * q].im,
+                                    (float)v[2 * q + 1].re, (float)v[2 * q + 1].im);
+        }
+        double2 *pw = reinterpret_cast<double2 *>(weight + base);
+        for (int q = 0; q < NPOL / 2; ++q) pw[q] = make_double2(w[2 * q], w[2 * q + 1]);
+    } else {
+        for (int p = 0; p < NPOL; ++p) {
+            store_c(vis, C128, base + p, v[p]);
+            weight[base + p] = w[p];
+        }
+    }
+}
+
+template <int NPOL, bool C128, bool VEC>
+__global__ __launch_bounds__(kThreads) void k_apply_chain(Shape s, void *vis, double *weight,
+                                                          const int32_t *__restrict__ ant1,
+                                                          const int32_t *__restrict__ ant2,
+                                                          int nants, int inverse, Chain c) {
+    const int64_t n = s.ntimes * s.nbl * s.nchan;
+    const int64_t e = blockIdx.x * (int64_t)kThreads + threadIdx.x;
+    if (e >= n) return;
+    const int f = (int)(e % s.nchan);
+    const int64_t tb = e / s.nchan;
+    const int b = (int)(tb % s.nbl);
+    const int64_t t = tb / s.nbl;
+    // the gain row of every table at this time; a row outside its table is
+    // taken as absent rather than read
+    int rows[kMaxChain];
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < kMaxChain; ++k) {
+        rows[k] = -1;
+        if (k < c.ntab) {
+            const int r = c.t[k].time_row[t];
+            if (r >= 0 && r < c.t[k].nrow_g) {
+                rows[k] = r;
+                any = true;
+            }
+        }
+    }
+    if (!any) return;
+    const size_t base = (size_t)e * NPOL;
+    const int a1 = ant1[b], a2 = ant2[b];
+    cplx v[4];
+    double w[4];
+    load_element<NPOL, C128, VEC>(vis, weight, base, v, w);
+#pragma unroll
+    for (int k = 0; k < kMaxChain; ++k) {
+        if (rows[k] < 0) continue;
+        apply_element(v, w, NPOL, f, rows[k], a1, a2, c.t[k].lg, c.t[k].ok, nants,
+                      c.t[k].nchan_g, c.t[k].nrec, inverse);
+        if constexpr (!C128) {
+            // the rounding of the store between two launches
+            for (int p = 0; p < NPOL; ++p)
+                v[p] = {(double)(float)v[p].re, (double)(float)v[p].im};
+        }
+    }
+    store_element<NPOL, C128, VEC>(vis, weight, base, v, w);
+}
+
+template <int NPOL, bool C128>
+void launch_chain(bool vec, unsigned grid, hipStream_t st, Shape s, void *vis, double *weight,
+                  const int32_t *ant1, const int32_t *ant2, int nants, int inverse,
+                  const Chain &c) {
+    if (vec)
+        k_apply_chain<NPOL, C128, true><<<grid, kThreads, 0, st>>>(s, vis, weight, ant1, ant2,
+                                                                   nants, inverse, c);
+    else
+        k_apply_chain<NPOL, C128, false><<<grid, kThreads, 0, st>>>(s, vis, weight, ant1, ant2,
+                                                                    nants, inverse, c);
 }
 
 Shape make_shape(int64_t ntimes, int nbl, int nchan, int npol) {
@@ -433,6 +582,60 @@ int sdp_hip_apply_gains(int64_t ntimes, int nbl, int nchan, int npol, void *vis,
         k_apply<<<(unsigned)((n + kThreads - 1) / kThreads), kThreads, 0, st>>>(
             s, vis, vis_dtype == SDP_HIP_C128, weight, flags, flags ? flag_bytes : 0, ant1, ant2,
             time_row, row_flag, lg, ok, nants, nchan_g, nrec, inverse);
+        SDP_HIP_CHECK(hipGetLastError());
+    });
+}
+
+int sdp_hip_apply_gain_chain(int64_t ntimes, int nbl, int nchan, int npol, void *vis,
+                             int vis_dtype, double *weight, const int32_t *ant1,
+                             const int32_t *ant2, int nants, int ntab, const void *const *gains,
+                             const int32_t *const *time_rows, const int32_t *nrow_g,
+                             const int32_t *nchan_g, const int32_t *nrec, int inverse,
+                             void *stream, char *errbuf, size_t errbuf_len) {
+    using namespace sdp;
+    using namespace sdp::calops;
+    return guarded(errbuf, errbuf_len, [&] {
+        const Shape s = make_shape(ntimes, nbl, nchan, npol);
+        check_common(vis_dtype, nullptr, 0);
+        SDP_REQUIRE(ntab >= 1 && ntab <= kMaxChain, "ntab must be 1 to SDP_HIP_GAIN_CHAIN_MAX");
+        SDP_REQUIRE(gains && time_rows && nrow_g && nchan_g && nrec, "null pointer argument");
+        SDP_REQUIRE(nants > 0, "bad gain table dimensions");
+        size_t off[kMaxChain + 1] = {0};
+        for (int k = 0; k < ntab; ++k) {
+            SDP_REQUIRE(nrec[k] == 1 || nrec[k] == 2, "nrec must be 1 or 2");
+            SDP_REQUIRE(npol == 1 || nrec[k] == 2, "npol 2 and 4 need 2x2 gains");
+            SDP_REQUIRE(nrow_g[k] >= 0 && nchan_g[k] > 0, "bad gain table dimensions");
+            off[k + 1] = off[k] + (size_t)nrow_g[k] * nants * nchan_g[k];
+        }
+        const int64_t n = ntimes * nbl * (int64_t)nchan;
+        if (n == 0 || off[ntab] == 0) return;
+        SDP_REQUIRE(vis && weight && ant1 && ant2, "null pointer argument");
+        const hipStream_t st = as_stream(stream);
+        // per-table regions of one scratch pair; 4 double2 per gain whatever nrec
+        double2 *lg = scratch<double2>("chain_lgain", off[ntab] * 4);
+        uint8_t *ok = scratch<uint8_t>("chain_ok", off[ntab]);
+        Chain c;
+        c.ntab = ntab;
+        for (int k = 0; k < ntab; ++k) {
+            const int64_t ng = (int64_t)(off[k + 1] - off[k]);
+            SDP_REQUIRE(time_rows[k] && (gains[k] || ng == 0), "null pointer argument");
+            c.t[k] = ChainTable{lg + off[k] * 4, ok + off[k], time_rows[k], nrow_g[k], nchan_g[k],
+                                nrec[k]};
+            if (ng)
+                k_gain_prep<<<(unsigned)((ng + 127) / 128), 128, 0, st>>>(
+                    ng, nrec[k], inverse, static_cast<const double2 *>(gains[k]),
+                    lg + off[k] * 4, ok + off[k]);
+        }
+        for (int k = ntab; k < kMaxChain; ++k)
+            c.t[k] = ChainTable{nullptr, nullptr, nullptr, 0, 1, 1};
+        const bool c128 = vis_dtype == SDP_HIP_C128;
+        const bool vec = reinterpret_cast<uintptr_t>(vis) % 16 == 0 &&
+                         reinterpret_cast<uintptr_t>(weight) % 16 == 0;
+        const unsigned grid = (unsigned)((n + kThreads - 1) / kThreads);
+        const auto launch = npol == 1   ? (c128 ? launch_chain<1, true> : launch_chain<1, false>)
+                            : npol == 2 ? (c128 ? launch_chain<2, true> : launch_chain<2, false>)
+                                        : (c128 ? launch_chain<4, true> : launch_chain<4, false>);
+        launch(vec, grid, st, s, vis, weight, ant1, ant2, nants, inverse, c);
         SDP_HIP_CHECK(hipGetLastError());
     });
 }

@@ -50,6 +50,7 @@ SDP_HIP_MIX_NAN_OUTPUT = 2
 SDP_HIP_GATHER_FACETS_MAX = 256
 SDP_HIP_SEGMENT_TILE = 32
 SDP_HIP_SEGMENT_KERNEL_MAX = 15
+SDP_HIP_GAIN_CHAIN_MAX = 8
 
 c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
@@ -201,6 +202,10 @@ SIGNATURES = {
     "sdp_hip_apply_gains": [
         c_i64, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp,
         c_vp, c_int, c_int, c_int, c_int, c_int, c_vp] + _ERR,
+    "sdp_hip_apply_gain_chain": [
+        c_i64, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp,  # shape, vis, dtype, weight, ants
+        c_int, c_int, c_vp, c_vp,                 # nants, ntab, gains (host), time_rows (host)
+        c_vp, c_vp, c_vp, c_int, c_vp] + _ERR,    # nrow_g, nchan_g, nrec (host), inverse, stream
     "sdp_hip_grid_weights": [
         c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_int,
         c_int, c_vp, c_vp, c_vp] + _ERR,

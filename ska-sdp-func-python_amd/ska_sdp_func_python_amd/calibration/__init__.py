@@ -1,3 +1,16 @@
-"""Calibration hot path: solve_gaintable (batched StefCal on MI355X) and apply_gaintable."""
-from .operations import apply_gaintable  # noqa: F401
+"""Calibration: solve_gaintable (batched StefCal on MI355X), apply_gaintable,
+chains of gain tables (calibrate_chain, solve_calibrate_chain,
+apply_calibration_chain) and gain-table operations."""
+from .chain_calibration import (  # noqa: F401
+    apply_calibration_chain,
+    calibrate_chain,
+    create_calibration_controls,
+    solve_calibrate_chain,
+)
+from .jones import apply_jones  # noqa: F401
+from .operations import (  # noqa: F401
+    apply_gaintable,
+    concatenate_gaintables,
+    multiply_gaintables,
+)
 from .solvers import solve_gaintable  # noqa: F401

@@ -454,8 +454,15 @@ class _FlatCopyArray(np.ndarray):
 
 
 class _QA:
-    def __init__(self, data):
+    def __init__(self, data, origin=None, context=None):
         self.data = data
+        self.origin = origin
+        self.context = context
+
+    def __str__(self):
+        lines = [f"Quality assessment: origin {self.origin}, context {self.context}"]
+        lines += [f"    {k}: {v}" for k, v in self.data.items()]
+        return "\n".join(lines)
 
 
 def _host(a):
@@ -763,6 +770,28 @@ class _GTAcc:
     def ntimes(self):
         return self._g._vars["gain"].shape[0]
 
+    def qa_gain_table(self, context=None):
+        """Amplitude and phase statistics of the gains with weight > 0 and the
+        largest residual of the rows with any weight (ska-sdp-datamodels'
+        GainTableAccessor.qa_gain_table); NaN where nothing has weight."""
+        gain = np.asarray(_host(self._g._vars["gain"]))
+        weight = np.asarray(_host(self._g._vars["weight"]))
+        residual = np.asarray(_host(self._g._vars["residual"]))
+        amp, phase = np.abs(gain[weight > 0.0]), np.angle(gain[weight > 0.0])
+        res = residual[np.sum(weight, axis=1) > 0.0]
+
+        def stat(fn, a):
+            return float(fn(a)) if a.size else float("nan")
+
+        data = {"shape": tuple(gain.shape)}
+        for tag, a in (("amp", amp), ("phase", phase)):
+            data[f"maxabs-{tag}"] = stat(np.max, a)
+            data[f"minabs-{tag}"] = stat(np.min, a)
+            data[f"rms-{tag}"] = stat(np.std, a)
+            data[f"medianabs-{tag}"] = stat(np.median, a)
+        data["residual"] = stat(np.max, res)
+        return _QA(data, origin="qa_gain_table", context=context)
+
 
 class GainTable(Dataset):
     @classmethod
@@ -783,10 +812,10 @@ class GainTable(Dataset):
 
 
 def create_gaintable_from_visibility(vis, timeslice=None, jones_type="T"):
-    """One gain row per time slot (``timeslice`` seconds, default every
-    integration); nchan = 1 for T/G jones, = vis nchan for B."""
+    """One gain row per time slot (``timeslice`` seconds; None, "auto" or a
+    value <= 0: every integration); nchan = 1 for T/G jones, = vis nchan for B."""
     times = np.asarray(vis.time.data)
-    if timeslice is None or timeslice == "auto":
+    if timeslice is None or timeslice == "auto" or timeslice <= 0.0:
         gain_times = times.copy()
         interval = np.asarray(vis.integration_time.data, float).copy()
         if len(times) > 1:

@@ -961,6 +961,52 @@ def apply_gains(vis, weight, flags, use_flags, ant1, ant2, time_row, gain, inver
     return vis, weight
 
 
+GAIN_CHAIN_MAX = _lib.SDP_HIP_GAIN_CHAIN_MAX
+
+
+def apply_gain_chain(vis, weight, ant1, ant2, time_rows, gains, inverse):
+    """The gain tables ``gains`` (each complex128 [rows, nants, nchan_g, nrec,
+    nrec]) with their time-row maps ``time_rows`` (each int32 [ntimes], -1 =
+    no row) applied in order, in place on device vis / weight [t, b, f, p]:
+    bit for bit what one ``apply_gains(..., use_flags=False)`` per table
+    gives, in one pass over vis and weight per group of up to
+    ``GAIN_CHAIN_MAX`` tables (sdp_hip_apply_gain_chain)."""
+    _vis4(vis, "vis")
+    nt, nbl, nchan, npol = vis.shape
+    if weight.shape != vis.shape or weight.dtype != torch.float64 or not weight.is_contiguous():
+        raise ValueError("weight must be contiguous float64 shaped like vis")
+    gains, time_rows = list(gains), list(time_rows)
+    if len(gains) != len(time_rows):
+        raise ValueError("one time_row map per gain table")
+    for a in (ant1, ant2):
+        _on_gpu(a, "ant1 / ant2")
+        if a.dtype != torch.int32 or a.numel() != nbl or not a.is_contiguous():
+            raise ValueError("ant1 / ant2 must be contiguous int32 [nbl]")
+    nants = gains[0].shape[1] if gains and gains[0].dim() == 5 else 1
+    for g, tr in zip(gains, time_rows):
+        _on_gpu(g, "gain")
+        _on_gpu(tr, "time_row")
+        if g.dtype != torch.complex128 or g.dim() != 5 or not g.is_contiguous():
+            raise ValueError("gain must be contiguous complex128 [rows, nants, nchan, nrec, nrec]")
+        if g.shape[1] != nants or g.shape[3] != g.shape[4]:
+            raise ValueError("the tables of a chain share nants; gains are nrec x nrec")
+        if tr.dtype != torch.int32 or tr.numel() != nt or not tr.is_contiguous():
+            raise ValueError("time_row must be contiguous int32 [ntimes]")
+    i32 = ctypes.c_int32
+    for k0 in range(0, max(len(gains), 1), GAIN_CHAIN_MAX):  # an empty chain: the entry refuses
+        gs, trs = gains[k0:k0 + GAIN_CHAIN_MAX], time_rows[k0:k0 + GAIN_CHAIN_MAX]
+        n = len(gs)
+        _lib.call("sdp_hip_apply_gain_chain", nt, nbl, nchan, npol, _ptr(vis),
+                  _DT_CODE[vis.dtype], _ptr(weight), _ptr(ant1), _ptr(ant2), int(nants), n,
+                  (ctypes.c_void_p * (n + 1))(*[g.data_ptr() for g in gs]),
+                  (ctypes.c_void_p * (n + 1))(*[t.data_ptr() for t in trs]),
+                  (i32 * (n + 1))(*[g.shape[0] for g in gs]),
+                  (i32 * (n + 1))(*[g.shape[2] for g in gs]),
+                  (i32 * (n + 1))(*[g.shape[3] for g in gs]), int(bool(inverse)),
+                  _stream(vis.device))
+    return vis, weight
+
+
 # ---- visibility operations (sdp_hip_vis_average_channels / to_stokes / remove_continuum)
 MAX_CONTINUUM_DEGREE = 5
 
