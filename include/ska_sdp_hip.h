@@ -994,6 +994,49 @@ int sdp_hip_segment_peaks(int nplanes, int ny, int nx, const void *planes,
                           int64_t *indices, void *stream, char *errbuf,
                           size_t errbuf_len);
 
+/* ---- batched 2-D Gaussian fits (fit_skycomponent) -------------------------------
+ * sdp_hip_gauss_fit: nfit independent least-squares fits of a rotated
+ * Gaussian to windows of SDP_HIP_GAUSS_FIT_WINDOW x SDP_HIP_GAUSS_FIT_WINDOW
+ * pixels (reference src/ska_sdp_func_python/sky_component/operations.py:
+ * 835-916, astropy's LevMarLSQFitter on a Gaussian2D).
+ *
+ * planes, row_strides, x0 and y0 are HOST tables of length nfit.  planes[f]
+ * is a DEVICE pointer to pixel (0, 0) of the plane that fit f reads, of type
+ * dtype (SDP_HIP_F32 or SDP_HIP_F64, one for the call); row_strides[f] its
+ * row stride in elements; the x stride is 1.  The window's first pixel is
+ * (row y0[f], column x0[f]); the caller guarantees that the window lies on the
+ * plane.  Different fits may read different planes, views of a cube or images
+ * of their own, of different sizes.  The library copies the tables to device
+ * scratch; they may be freed when the call returns.  The planes are only read.
+ * The call only enqueues work on `stream`.
+ *
+ * params is a device array [nfit][6]: amplitude, x_mean, y_mean, x_stddev,
+ * y_stddev, theta, the means in the plane's pixel coordinates, of
+ *   g = A exp(-(a dx^2 + b dx dy + c dy^2))
+ *   a = (cos^2 t / sx^2 + sin^2 t / sy^2) / 2
+ *   b = (sin 2t / sx^2 - sin 2t / sy^2) / 2
+ *   c = (sin^2 t / sx^2 + cos^2 t / sy^2) / 2
+ * minimising the unweighted sum over the window of (g - z)^2, in fp64 whatever
+ * the pixel type, both standard deviations bounded below by FLT_MIN.  The
+ * start is A = max z, the means at the window's centre pixel, sx = sy = 1,
+ * t = 0.  The solver is Levenberg-Marquardt in More's trust-region form (the
+ * algorithm of MINPACK's lmder) on the normal equations, run until the trust
+ * radius falls below 1e-12 |D x| or the cost no longer decreases in fp64; at
+ * most max_iter (>= 1) model evaluations.
+ *
+ * status (device int32 [nfit]): 0 converged, 1 max_iter reached (params hold
+ * the last accepted iterate), 2 a window pixel or an iterate was not finite
+ * (params are NaN).  niter (device int32 [nfit], or NULL) receives the number
+ * of model evaluations.  A fit's result depends on its window and its
+ * position alone: not on nfit, nor on what else the call fits.
+ */
+#define SDP_HIP_GAUSS_FIT_WINDOW 15
+int sdp_hip_gauss_fit(int nfit, const void *const *planes, int dtype,
+                      const int64_t *row_strides, const int32_t *x0,
+                      const int32_t *y0, int max_iter, double *params,
+                      int32_t *status, int32_t *niter, void *stream,
+                      char *errbuf, size_t errbuf_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,7 @@ SDP_HIP_GATHER_FACETS_MAX = 256
 SDP_HIP_SEGMENT_TILE = 32
 SDP_HIP_SEGMENT_KERNEL_MAX = 15
 SDP_HIP_GAIN_CHAIN_MAX = 8
+SDP_HIP_GAUSS_FIT_WINDOW = 15
 
 c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
@@ -267,6 +268,9 @@ SIGNATURES = {
     "sdp_hip_segment_peaks": [
         c_int, c_int, c_int, c_vp, c_int, c_i64,  # nplanes, ny, nx, planes, dtype, plane stride
         c_vp, c_int, c_vp, c_vp, c_vp] + _ERR,    # segmap, nseg, values, indices, stream
+    "sdp_hip_gauss_fit": [
+        c_int, c_vp, c_int, c_vp, c_vp, c_vp,     # nfit, planes (host), dtype, strides, x0, y0 (host)
+        c_int, c_vp, c_vp, c_vp, c_vp] + _ERR,    # max_iter, params, status, niter, stream
 }
 
 _lock = threading.Lock()

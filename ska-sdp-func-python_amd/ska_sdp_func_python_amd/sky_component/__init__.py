@@ -10,17 +10,22 @@ from .operations import (  # noqa: F401
     find_skycomponent_matches,
     find_skycomponent_matches_atomic,
     find_skycomponents,
+    fit_skycomponent,
     fit_skycomponent_spectral_index,
+    fit_skycomponents,
     image_voronoi_iter,
     insert_skycomponent,
+    partition_skycomponent_neighbours,
     remove_neighbouring_components,
     restore_skycomponent,
     segment_image,
     select_components_by_separation,
+    select_neighbouring_components,
     voronoi_decomposition,
 )
 from .taylor_terms import (  # noqa: F401
     calculate_skycomponent_list_taylor_terms,
+    find_skycomponents_frequency_taylor_terms,
     gather_skycomponents_from_channels,
     interpolate_skycomponents_frequency,
     transpose_skycomponents_to_channels,

@@ -19,8 +19,14 @@ find_skycomponents (:256-363) turns an image back into components: channel
 mean, smoothing, 8-connected segmentation and the per-channel peak search run
 on the device (csrc/segment.hip), the O(segments x channels) rest on the host.
 segment_image returns its segment map.  The catalogue helpers that follow a
-find (:65-253, :565-580, :919-943) are small host functions; astropy's
-catalogue matching is replaced by SkyCoord.separation.
+find (:65-253, :565-580, :818-832, :919-943) are small host functions;
+astropy's catalogue matching is replaced by SkyCoord.separation.
+
+fit_skycomponent (:835-916) fits a rotated Gaussian to the 15 x 15 pixels about
+a component: the fit runs on the device (csrc/gaussfit.hip, one wavefront per
+window), the O(components) rest -- window placement, direction, the pixel the
+flux is read at, shape and params -- on the host in fitted_skycomponent.
+fit_skycomponents does the fits of many components in many images in one launch.
 """
 
 import collections.abc
@@ -41,7 +47,9 @@ __all__ = ["apply_beam_to_skycomponent", "insert_skycomponent", "restore_skycomp
            "find_nearest_skycomponent", "find_separation_skycomponents",
            "find_skycomponent_matches_atomic", "find_skycomponent_matches",
            "select_components_by_separation", "remove_neighbouring_components",
-           "filter_skycomponents_by_flux", "fit_skycomponent_spectral_index"]
+           "filter_skycomponents_by_flux", "fit_skycomponent_spectral_index",
+           "fit_skycomponent", "fit_skycomponents", "fitted_skycomponent",
+           "select_neighbouring_components", "partition_skycomponent_neighbours"]
 
 log = logging.getLogger("func-python-logger")
 
@@ -510,7 +518,186 @@ def find_skycomponents(im, fwhm=1.0, threshold=1.0, npixels=5):
             for k in range(nlabels)]
 
 
-# ---- catalogue helpers (:65-253, :565-580, :919-943) ----------------------------
+# ---- fit_skycomponent ---------------------------------------------------------------
+FIT_HALF_WINDOW = kernels.GAUSS_FIT_WINDOW // 2
+_SIGMA_TO_FWHM = 2.0 * np.sqrt(2.0 * np.log(2.0))
+
+
+def _image_x(im):
+    """The image's "x" coordinate as ska-sdp-datamodels' Image builds it, in
+    degrees: nx points from crval - cdelt nx / 2 in steps of cdelt."""
+    w = im.image_acc.wcs.wcs
+    nx = int(im["pixels"].data.shape[3])
+    cellsize = np.abs(w.cdelt[1])
+    return np.linspace(w.crval[0] - cellsize * nx / 2, w.crval[0] + cellsize * nx / 2, nx,
+                       endpoint=False)
+
+
+def fitted_skycomponent(im, sc, params, status, flux_at, **kwargs):
+    """The host half of fit_skycomponent (reference :854-916): the component
+    that the fit's parameters make of ``sc``.
+
+    :param im: Image (its WCS and shape are used, not its pixels)
+    :param sc: the SkyComponent that was fitted
+    :param params: the fit's (amplitude, x_mean, y_mean, x_stddev, y_stddev,
+        theta), the means in 0-based pixels
+    :param status: kernels.gauss_fit's status, or None when the window did not
+        lie wholly on the image
+    :param flux_at: callable (iy, ix) -> the image's pixels[:, :, iy, ix] as a
+        numpy array [nchan, npol]; called only for a pixel on the image
+    :param force_point_sources: keep the shape "Point" (default True)
+    :return: the new SkyComponent; ``sc`` itself when there was no fit
+    """
+    if status is None:
+        log.warning("fit_skycomponent: fit failed  the fitting window of %s does not lie on "
+                    "the image", sc.name)
+        return sc
+    if status == 2:
+        log.warning("fit_skycomponent: fit failed  %s: a pixel of the window or an iterate is "
+                    "not finite", sc.name)
+        return sc
+    if status == 1:
+        log.warning("fit_skycomponent: the fit of %s reached its iteration limit; the last "
+                    "iterate is used", sc.name)
+    ny, nx = (int(n) for n in im["pixels"].data.shape[2:])
+    x_mean, y_mean = float(params[1]), float(params[2])
+    newsc = sc.copy()
+    newsc.direction = pixel_to_skycoord(x_mean, y_mean, im.image_acc.wcs, 0)
+    iy = round(y_mean)
+    ix = round(x_mean)
+    # (the reference: "We could fit each frequency separately. For the moment, we just scale")
+    if 0 <= iy < ny and 0 <= ix < nx:
+        newsc.flux = np.asarray(flux_at(iy, ix))
+    try:
+        force_point_sources = kwargs["force_point_sources"]
+    except KeyError:
+        log.info("fit_skycomponent: force_point_sources not give, setting as default: True")
+        force_point_sources = True
+    x_fwhm = float(params[3]) * _SIGMA_TO_FWHM
+    y_fwhm = float(params[4]) * _SIGMA_TO_FWHM
+    theta = float(params[5])
+    if force_point_sources or (x_fwhm <= 0.0 or y_fwhm <= 0.0):
+        newsc.shape = "Point"
+    else:
+        x = _image_x(im)
+        # the reference's cellsize: the span of the x coordinate over its length, not cdelt
+        cellsize = np.abs(x[0] - x[-1]) / len(x)
+        if y_fwhm > x_fwhm:
+            clean_gaussian = {"bmaj": np.rad2deg(y_fwhm * cellsize),
+                              "bmin": np.rad2deg(x_fwhm * cellsize),
+                              "bpa": np.rad2deg(theta)}
+        else:
+            clean_gaussian = {"bmaj": np.rad2deg(x_fwhm * cellsize),
+                              "bmin": np.rad2deg(y_fwhm * cellsize),
+                              "bpa": np.rad2deg(theta) + 90.0}
+        newsc.shape = "Gaussian"
+        newsc.params = clean_gaussian
+    return newsc
+
+
+def fit_skycomponents(images, comps, **kwargs):
+    """Fit every component of ``comps`` in every image of ``images`` with a
+    two-dimensional Gaussian: ``len(images) x len(comps)`` fits in one kernel
+    launch and one gather of fluxes per image.  Not in the reference, whose
+    fit_skycomponent is the 1 x 1 case.
+
+    :param images: an Image or a list of Images; pixels float64 or float32
+        [nchan, npol, ny, nx], numpy or device tensors
+    :param comps: list of SkyComponents
+    :param force_point_sources: keep the shape "Point" (default True)
+    :param max_iter: cap on the model evaluations of a fit (default 100)
+    :return: list over the images of lists over the components of
+        SkyComponents, as fit_skycomponent returns them
+    """
+    import torch
+    images = [images] if isinstance(images, Image) else list(images)
+    comps = list(comps)
+    max_iter = kwargs.pop("max_iter", 100)
+    window = kernels.GAUSS_FIT_WINDOW
+    dev_pixels, jobs = [], []   # jobs: (image, component, x0, y0)
+    for i, im in enumerate(images):
+        pixels = im["pixels"].data
+        _, _, ny, nx = _check_pixels(pixels, "fit_skycomponent")
+        dev_pixels.append(pixels if _device.is_device(pixels) else _device.to_dev(pixels))
+        if not comps:
+            continue
+        px, py = skycoord_to_pixel([c.direction for c in comps], im.image_acc.wcs, origin=0)
+        for k in range(len(comps)):
+            if not (np.isfinite(px[k]) and np.isfinite(py[k])):
+                continue
+            x0 = int(np.round(px[k])) - FIT_HALF_WINDOW
+            y0 = int(np.round(py[k])) - FIT_HALF_WINDOW
+            if 0 <= x0 and x0 + window <= nx and 0 <= y0 and y0 + window <= ny:
+                jobs.append((i, k, x0, y0))
+    fits = {}
+    for dtype in sorted({t.dtype for t in dev_pixels}, key=str):   # one call per pixel type
+        mine = [j for j in jobs if dev_pixels[j[0]].dtype == dtype]
+        if not mine:
+            continue
+        plane = [t[0, 0] for t in dev_pixels]   # one view per image, shared by its fits
+        params, status, _ = kernels.gauss_fit([plane[j[0]] for j in mine], [j[2] for j in mine],
+                                              [j[3] for j in mine], max_iter)
+        params, status = params.cpu().numpy(), status.cpu().numpy()
+        for n, (i, k, _, _) in enumerate(mine):
+            fits[(i, k)] = (params[n], int(status[n]))
+    out = []
+    for i, im in enumerate(images):
+        ny, nx = (int(n) for n in dev_pixels[i].shape[2:])
+        # the pixels that the fitted centres round to, gathered on the device in one go
+        wanted = {}
+        for k in range(len(comps)):
+            if (i, k) in fits and fits[(i, k)][1] != 2:
+                iy, ix = round(float(fits[(i, k)][0][2])), round(float(fits[(i, k)][0][1]))
+                if 0 <= iy < ny and 0 <= ix < nx:
+                    wanted[(iy, ix)] = None
+        if wanted:
+            at = lambda v: torch.as_tensor(v, dtype=torch.int64, device=dev_pixels[i].device)
+            flux = dev_pixels[i][:, :, at([p[0] for p in wanted]), at([p[1] for p in wanted])]
+            flux = flux.permute(2, 0, 1).cpu().numpy()
+            for n, pixel in enumerate(wanted):
+                wanted[pixel] = flux[n]
+        row = []
+        for k, sc in enumerate(comps):
+            params, status = fits.get((i, k), (None, None))
+            row.append(fitted_skycomponent(im, sc, params, status,
+                                           lambda iy, ix: wanted[(iy, ix)], **kwargs))
+        out.append(row)
+    return out
+
+
+def fit_skycomponent(im, sc, **kwargs):
+    """Fit a two-dimensional Gaussian to a SkyComponent (reference :835-916).
+
+    Plane [0, 0] of the image is fitted on the 15 x 15 pixels about the pixel
+    nearest to the component (numpy.round of its 0-based pixel location) with
+    astropy's Gaussian2D, from the reference's start (the window's maximum, its
+    centre, standard deviations 1, theta 0), by csrc/gaussfit.hip.  The new
+    component has the direction of the fitted centre and the flux of the pixel
+    nearest to it (Python's round), all channels and polarisations, when that
+    pixel is on the image; its shape is "Point" with ``force_point_sources``
+    (default True) or a non-positive width, else "Gaussian" with ``params``
+    bmaj, bmin, bpa in degrees as the reference forms them.  Device pixels
+    stay on the device: only the six parameters and [nchan, npol] fluxes come
+    to the host.
+
+    Where the window does not lie wholly on the image the component is
+    returned unchanged and a warning logged, as the reference does through its
+    ``except ValueError``.  Where this differs from the reference: a window
+    with a pixel that is not finite, or a fit whose iterates leave the finite
+    numbers, also returns the component unchanged; the fit is run to a tighter
+    stop (a relative step of 1e-12, or a cost that no longer decreases; the
+    reference: 1e-7 and 1.49e-8); at the cap of 100 model evaluations the last
+    iterate is used and a warning logged; numpy pixels go through the device.
+
+    :param im: Image; pixels float64 or float32, numpy or a device tensor
+    :param sc: SkyComponent
+    :param force_point_sources: keep the shape "Point" (default True)
+    :return: the fitted SkyComponent
+    """
+    return fit_skycomponents(im, [sc], **kwargs)[0][0]
+
+
+# ---- catalogue helpers (:65-253, :565-580, :818-832, :919-943) --------------------
 # astropy's catalogue matching is replaced by the separations themselves:
 # nearest is the smallest separation, the first on ties.
 def find_nearest_skycomponent_index(home, comps):
@@ -568,6 +755,28 @@ def find_skycomponent_matches(comps_test, comps_ref, tol=1e-7):
 def select_components_by_separation(home, comps, rmax=2 * np.pi, rmin=0.0):
     """The components whose separation from ``home`` lies in [rmin, rmax] rad."""
     return [comp for comp in comps if rmin <= comp.direction.separation(home).rad <= rmax]
+
+
+def select_neighbouring_components(comps, target_comps):
+    """Assign every component to the nearest target (reference :205-225).
+
+    :return: the index in ``target_comps`` of the target nearest to each
+        component (int array) and the separations in rad (float array; the
+        reference returns astropy Angles)
+    """
+    if len(comps) and len(target_comps) == 0:
+        raise ValueError("select_neighbouring_components: Catalog is empty")
+    separations = find_separation_skycomponents(comps, target_comps)   # [target, comp]
+    idx = np.array([int(np.argmin(separations[:, k])) for k in range(len(comps))], dtype=int)
+    d2d = np.array([separations[idx[k], k] for k in range(len(comps))], dtype=float)
+    return idx, d2d
+
+
+def partition_skycomponent_neighbours(comps, targets):
+    """The components partitioned by their nearest target (reference :818-832):
+    one list per target that is nearest to some component, in target order."""
+    idx, _ = select_neighbouring_components(comps, targets)
+    return [[comp for comp, i in zip(comps, idx) if i == comp_id] for comp_id in np.unique(idx)]
 
 
 def remove_neighbouring_components(comps, distance):

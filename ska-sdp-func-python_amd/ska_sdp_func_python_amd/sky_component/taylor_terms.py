@@ -12,9 +12,11 @@ The weights are w_k = ((nu - nu_ref) / nu_ref) ** k as for images
 (image/taylor_terms.py), with ``numpy.linalg.pinv(coupling, rcond=1e-7)`` and
 ``numpy.polynomial.polynomial.polyfit`` / ``polyval`` as in the reference.
 
-``find_skycomponents_frequency_taylor_terms`` (:83-153) is left out: it needs
-``find_skycomponents``, which segments the image with photutils, and that
-package is not available to this project.
+``find_skycomponents_frequency_taylor_terms`` (:83-153) joins the device
+functions: moment 0 of the channel images (image/taylor_terms.py),
+``find_skycomponents`` on it and one batch of Gaussian fits, every component
+in every channel image (``fit_skycomponents``), then the two host functions
+above.
 """
 
 import logging
@@ -23,6 +25,7 @@ import numpy
 from numpy.polynomial import polynomial
 
 __all__ = ["calculate_skycomponent_list_taylor_terms",
+           "find_skycomponents_frequency_taylor_terms",
            "gather_skycomponents_from_channels",
            "interpolate_skycomponents_frequency",
            "transpose_skycomponents_to_channels"]
@@ -68,6 +71,62 @@ def calculate_skycomponent_list_taylor_terms(sc_list, nmoment=1, reference_frequ
             taylor_term_sc_list.append(taylor_term_sc)
         newsc_list.append(taylor_term_sc_list)
     return newsc_list
+
+
+def find_skycomponents_frequency_taylor_terms(dirty_list, nmoment=1, reference_frequency=None,
+                                              **kwargs):
+    """Find components in moment 0 of a list of channel images, fit each in
+    every channel, smooth the fluxes by a polynomial in frequency and return
+    them per channel (reference :83-153).
+
+    The components are those of ``find_skycomponents`` on the moment-0 image,
+    above ``component_threshold`` (default: infinity, which finds none).  Each
+    gets, per channel image, the Stokes fluxes ``fit_skycomponent(image,
+    component).flux[0, :]``; all of these fits run as one batch on the device.
+
+    :param dirty_list: list of single-channel Images at different frequencies
+    :param nmoment: number of polynomial terms fitted in frequency
+    :param reference_frequency: reference frequency (default: the centre image's)
+    :param component_threshold: threshold of the search in moment 0
+    :return: list over channels of lists of single-channel SkyComponents; ``[]``
+        when no component is found
+    """
+    from ..image.taylor_terms import calculate_frequency_taylor_terms_from_image_list
+    from .operations import find_skycomponents, fit_skycomponents
+    frequency = numpy.array([d.frequency[0] for d in dirty_list])
+    if reference_frequency is None:
+        reference_frequency = frequency[len(frequency) // 2]
+    log.debug("find_skycomponents_frequency_taylor_terms: Reference frequency = %.3f (MHz)",
+              1e-6 * reference_frequency)
+
+    moment0_list = calculate_frequency_taylor_terms_from_image_list(
+        dirty_list, nmoment=1, reference_frequency=reference_frequency)
+    threshold = kwargs.get("component_threshold", numpy.inf)
+    try:
+        moment0_skycomponents = find_skycomponents(moment0_list[0], threshold=threshold)
+    except ValueError:
+        log.info("find_skycomponents_frequency_taylor_terms: No skycomponents found in moment 0")
+        return []
+    ncomps = len(moment0_skycomponents)
+    if ncomps == 0:
+        return []
+    log.info("find_skycomponents_frequency_taylor_terms: found %s skycomponents in moment 0",
+             ncomps)
+
+    fit_kwargs = {k: v for k, v in kwargs.items() if k != "component_threshold"}
+    fitted = fit_skycomponents(dirty_list, moment0_skycomponents, **fit_kwargs)
+    found_component_list = []
+    for isc, sc in enumerate(moment0_skycomponents):
+        found_component = sc.copy()
+        found_component.frequency = frequency
+        found_component.flux = numpy.array([list(fitted[chan][isc].flux[0, :])
+                                            for chan in range(len(dirty_list))])
+        found_component_list.append(found_component)
+        log.info("Component %s: %s", isc, found_component)
+
+    interpolated_sc_list = interpolate_skycomponents_frequency(
+        found_component_list, nmoment=nmoment, reference_frequency=reference_frequency)
+    return transpose_skycomponents_to_channels(interpolated_sc_list)
 
 
 def interpolate_skycomponents_frequency(sc_list, nmoment=1, reference_frequency=None):
