@@ -1037,6 +1037,58 @@ int sdp_hip_gauss_fit(int nfit, const void *const *planes, int dtype,
                       int32_t *status, int32_t *niter, void *stream,
                       char *errbuf, size_t errbuf_len);
 
+/* ---- bandpass resampling (calibration/beamformer_utils.py) -----------------
+ * The gain spectra of a table re-channelised (reference src/
+ * ska_sdp_func_python/calibration/beamformer_utils.py:273-491).  gain is a
+ * device array [nrows][c_in][nrec][nrec] complex128, a row one (time,
+ * antenna) pair, out a device array [nrows][c_out][nrec][nrec] complex128,
+ * both contiguous and aligned to 16 bytes, nrec 1 or 2.  All tables are
+ * DEVICE arrays; the calls only enqueue work on `stream`, so the tables stay
+ * allocated until it has run.  A row's result depends on that row alone: the
+ * same bits alone, in any batch and on any run.  fp64, no contraction.
+ *
+ * sdp_hip_resample_polyfit: the unweighted least-squares polynomial of
+ * `degree` (0 .. SDP_HIP_BANDPASS_MAX_DEGREE) through the input channels
+ * edges[s] .. edges[s + 1] - 1 of each of nseg segments (1 ..
+ * SDP_HIP_BANDPASS_MAX_SEGMENTS; int32 edges[nseg + 1], ascending within
+ * 0 .. c_in), evaluated at the output channels.  The caller supplies the fit
+ * factored through polynomials p_0 .. p_degree that are orthonormal under the
+ * unit-weight inner product on their segment's input channels:
+ *   q[d][c]   (double [degree + 1][c_in])  p_d of the segment of c, at c
+ *   e[co][d]  (double [c_out][degree + 1]) p_d of segment seg[co], at co
+ *   seg[co]   (int32 [c_out]) the segment of output channel co, or -1
+ *   out[co] = sum_d e[co][d] * (sum_{c in seg[co]} q[d][c] * gain[c])
+ * per real and imaginary part of every matrix element.  An output channel
+ * with seg -1 (or a value outside 0 .. nseg - 1) is written NaN + NaN j.
+ * c_in >= 2.  The inner sums are formed by 256 lanes striding over the
+ * segment's channels, an xor butterfly over each wavefront's 64 lanes and
+ * the four wavefronts' values added in ascending order; the outer sum starts
+ * from e[co][0] * coef[0] and adds ascending d.
+ *
+ * sdp_hip_resample_interp: numpy.interp on complex data, bit for bit.
+ * x_in [c_in] and x_out [c_out] are the abscissae (double), interval [c_out]
+ * (int32) what the host's search gives for each x_out:
+ *   -2            x_out is NaN: the result is x_out + 0 j
+ *   -1            below x_in[0]: gain[0]
+ *   0 .. c_in-2   x_in[j] <= x_out < x_in[j + 1]: gain[j] if x_out == x_in[j],
+ *                 else per component slope = (y[j+1] - y[j]) * (1 / (x_in[j+1]
+ *                 - x_in[j])) and slope * (x_out - x_in[j]) + y[j]; if that is
+ *                 NaN, slope * (x_out - x_in[j+1]) + y[j+1]; if that is NaN
+ *                 too and y[j] == y[j+1], y[j]
+ *   >= c_in-1     at or above the last knot: gain[c_in - 1]
+ */
+#define SDP_HIP_BANDPASS_MAX_DEGREE 7
+#define SDP_HIP_BANDPASS_MAX_SEGMENTS 64
+int sdp_hip_resample_polyfit(int64_t nrows, int c_in, int c_out, int nrec,
+                             int degree, int nseg, const void *gain, void *out,
+                             const double *q, const double *e,
+                             const int32_t *seg, const int32_t *edges,
+                             void *stream, char *errbuf, size_t errbuf_len);
+int sdp_hip_resample_interp(int64_t nrows, int c_in, int c_out, int nrec,
+                            const void *gain, void *out, const double *x_in,
+                            const double *x_out, const int32_t *interval,
+                            void *stream, char *errbuf, size_t errbuf_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,8 @@ SDP_HIP_SEGMENT_TILE = 32
 SDP_HIP_SEGMENT_KERNEL_MAX = 15
 SDP_HIP_GAIN_CHAIN_MAX = 8
 SDP_HIP_GAUSS_FIT_WINDOW = 15
+SDP_HIP_BANDPASS_MAX_DEGREE = 7
+SDP_HIP_BANDPASS_MAX_SEGMENTS = 64
 
 c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
@@ -271,6 +273,12 @@ SIGNATURES = {
     "sdp_hip_gauss_fit": [
         c_int, c_vp, c_int, c_vp, c_vp, c_vp,     # nfit, planes (host), dtype, strides, x0, y0 (host)
         c_int, c_vp, c_vp, c_vp, c_vp] + _ERR,    # max_iter, params, status, niter, stream
+    "sdp_hip_resample_polyfit": [
+        c_i64, c_int, c_int, c_int, c_int, c_int,  # nrows, c_in, c_out, nrec, degree, nseg
+        c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp] + _ERR,  # gain, out, q, e, seg, edges, stream
+    "sdp_hip_resample_interp": [
+        c_i64, c_int, c_int, c_int,               # nrows, c_in, c_out, nrec
+        c_vp, c_vp, c_vp, c_vp, c_vp, c_vp] + _ERR,  # gain, out, x_in, x_out, interval, stream
 }
 
 _lock = threading.Lock()

@@ -1,6 +1,13 @@
 """Calibration: solve_gaintable (batched StefCal on MI355X), apply_gaintable,
 chains of gain tables (calibrate_chain, solve_calibrate_chain,
-apply_calibration_chain) and gain-table operations."""
+apply_calibration_chain), gain-table operations and the CBF beamformer
+utilities (bandpass resampling on the GPU)."""
+from .beamformer_utils import (  # noqa: F401
+    expand_delay_phase,
+    multiply_gaintable_jones,
+    resample_bandpass,
+    set_beamformer_frequencies,
+)
 from .chain_calibration import (  # noqa: F401
     apply_calibration_chain,
     calibrate_chain,

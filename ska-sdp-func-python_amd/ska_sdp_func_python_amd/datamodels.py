@@ -793,6 +793,17 @@ class _GTAcc:
         return _QA(data, origin="qa_gain_table", context=context)
 
 
+class Configuration:
+    """The array configuration as far as gain tables read it: its ``name``
+    ("LOW-AA0.5", "MID", ...)."""
+
+    def __init__(self, name=""):
+        self.name = name
+
+    def __repr__(self):
+        return f"Configuration('{self.name}')"
+
+
 class GainTable(Dataset):
     @classmethod
     def constructor(cls, gain, time, interval, weight, residual, frequency, receptor_frame,
@@ -806,6 +817,24 @@ class GainTable(Dataset):
     @property
     def gaintable_acc(self):
         return _GTAcc(self)
+
+    # what calibration/beamformer_utils.py reads: both receptor frames are the
+    # table's one frame, and the receptor coordinates index the Jones matrix
+    @property
+    def receptor_frame1(self):
+        return self.attrs["receptor_frame"]
+
+    @property
+    def receptor_frame2(self):
+        return self.attrs["receptor_frame"]
+
+    @property
+    def receptor1(self):
+        return _Derived(np.arange(self._vars["gain"].shape[3]))
+
+    @property
+    def receptor2(self):
+        return _Derived(np.arange(self._vars["gain"].shape[4]))
 
     def copy(self, deep=True, zero=False):
         return self._copy_with(deep=deep)
