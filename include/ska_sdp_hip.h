@@ -103,6 +103,13 @@ typedef struct sdp_hip_wgrid_info {
                              as their Hermitian mirrors (-u, -v, -w, conj), so
                              the plane passes ran over half the row band
                              (SDP_HIP_HFOLD=0 switches it off)              */
+    int layout_reused;    /* invert: the two-level sort's layout (bins, cell
+                             bases, pads, work items) was the one kept from
+                             the slot's previous invert of the same uvw, freq
+                             and geometry: only the value pass, a recount and
+                             the final move ran.  nvis_used then counts every
+                             in-grid visibility, zero weights included
+                             (SDP_HIP_LAYOUT_CACHE=0 switches it off)       */
 } sdp_hip_wgrid_info;
 
 /* Library/ABI version and a device probe. */
@@ -191,6 +198,18 @@ int sdp_hip_wstack_layout(const double *bounds, int npix_x, int npix_y,
                           double pixsize_x, double pixsize_y, double epsilon,
                           int do_wstacking, unsigned flags, sdp_hip_wgrid_info *info,
                           char *errbuf, size_t errbuf_len);
+
+/*
+ * sdp_hip_wstack_fingerprint -- the content fingerprint under which an invert
+ * keeps its bucketing layout (info.layout_reused), computed on the host from
+ * HOST arrays (no device work; the device computes the same words during the
+ * invert's bounds pass).  out = {uvw a, uvw b, freq a, freq b}: per array two
+ * 64-bit wrapping sums over its elements of a mix of (index, bit patterns) --
+ * independent of the order of summation, not of the order of the content.
+ */
+int sdp_hip_wstack_fingerprint(const double *uvw, int64_t uvw_row_stride, int64_t nrow,
+                               const double *freq, int nchan, uint64_t *out,
+                               char *errbuf, size_t errbuf_len);
 
 /*
  * sdp_hip_ms2dirty_vis -- sdp_hip_ms2dirty with the visibility-side prologue

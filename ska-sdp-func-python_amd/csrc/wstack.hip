@@ -14,6 +14,11 @@
 // drivers), call drivers, C ABI.
 //
 // An invert (ms2dirty), in call order:
+//   bounds_pass        a default invert: k_bounds first, for the content
+//                      fingerprint (wstack_fingerprint.h) of uvw and freq;
+//                      the slot's kept layout (KeptLayout) with that key
+//                      replaces plan_geometry, and bucket_tiled runs
+//                      values_only
 //   plan_geometry      k_bounds: w range and uv extent; support, padded
 //                      grid, plane layout, Hermitian fold, bucket window,
 //                      bucketing route, Plan flags, resident planes
@@ -1771,6 +1776,7 @@ struct TPoint {
     double wd;  // effective weight (0 outside the call's w slab)
     Coord c;
     bool in;
+    bool dead;  // count pass: in the grid, but dropped for its zero weight
 };
 
 template <bool kCount>
@@ -1778,6 +1784,7 @@ __device__ __forceinline__ TPoint t_classify(const Geo &g, const TLoad &L, const
                                              unsigned long long *nbad) {
     TPoint p;
     p.in = false;
+    p.dead = false;
     p.wd = 0.0;
     p.row = L.row;
     p.chan = (int)L.chan;
@@ -1785,13 +1792,18 @@ __device__ __forceinline__ TPoint t_classify(const Geo &g, const TLoad &L, const
     if (!L.live) return p;
     if (g.slab && slab_out_v(g, L.wm, L.s)) return p;
     p.wd = L.wd;
-    if (!(x.all || (float)p.wd != 0.0f)) return p;
+    // a zero weight drops the visibility (not from an x.all layout); the
+    // count pass still classifies it: a layout that lacks an in-grid
+    // visibility is not the x.all layout, and is not kept (KeptLayout)
+    const bool weighted = x.all || (float)p.wd != 0.0f;
+    if (!kCount && !weighted) return p;
     p.c = vis_coord_v(g, L.um, L.vm, L.wm, L.s);
     if (!p.c.ok) {
-        if (kCount && !p.c.skip) atomicAdd(nbad, 1ull);
+        if (kCount && weighted && !p.c.skip) atomicAdd(nbad, 1ull);
         return p;
     }
-    p.in = true;
+    p.dead = !weighted;
+    p.in = weighted;
     return p;
 }
 
@@ -1821,6 +1833,7 @@ __global__ __launch_bounds__(kT1Threads) void k_t_count(Geo g, int64_t nvis, int
     __syncthreads();
     const int64_t v0 = (int64_t)blockIdx.x * vpw, v1 = min(nvis, v0 + vpw);
     double ws = 0.0;
+    bool dead = false;
     for (int64_t base = v0; base < v1; base += (int64_t)kT1Threads * kTUc) {
         TLoad L[kTUc];
 #pragma unroll
@@ -1831,10 +1844,14 @@ __global__ __launch_bounds__(kT1Threads) void k_t_count(Geo g, int64_t nvis, int
         for (int u = 0; u < kTUc; ++u) {
             const TPoint p = t_classify<true>(g, L[u], x, nbad);
             ws += p.wd;
+            dead |= p.dead;
             lds_run_add<false>(p.in ? tiled_key(g, p.c) >> 12 : 0u, p.in, hist);
         }
     }
     if (sw_slots) t_weight_sum(ws, sw_slots);
+    // nbad[1]: waves that dropped an in-grid visibility for its zero weight
+    // (one atomic per such wave; only zero or not matters)
+    if (__any(dead) && (threadIdx.x & 63) == 0) atomicAdd(nbad + 1, 1ull);
     __syncthreads();
     // the workgroup's slice of every non-empty bin (its offset inside the bin)
     unsigned *row = m1 + (size_t)blockIdx.x * nb;
@@ -2107,7 +2124,8 @@ __global__ __launch_bounds__(256) void k_t_segscan(const TSeg *__restrict__ segs
 // prefix of the segment totals over the bin's segments (in place in S), the
 // cell total T, and into binsum[bin] the slice's (padded records << 32 |
 // items) -- a group of 16 cells is 16 consecutive lanes; its items are its
-// padded records in chunks of `chunk`
+// padded records in chunks of `chunk`.  binsum == nullptr: the prefix only
+// (bucket_tiled's recount on a kept layout)
 template <bool PAD>
 __global__ __launch_bounds__(256) void k_t_cellcol(const unsigned *__restrict__ nbl,
                                                    const unsigned *__restrict__ segb,
@@ -2139,6 +2157,8 @@ __global__ __launch_bounds__(256) void k_t_cellcol(const unsigned *__restrict__ 
             q[(size_t)k * kBinCells] = run;
             run += v;
         }
+        // (a recount over kept bins: the cells' totals and the bin sums hold)
+        if (!binsum) continue;
         tot[(size_t)b * kBinCells + cell] = run;
         const unsigned pd = PAD ? (run + 3u) & ~3u : run;
         unsigned gt = pd;
@@ -2163,7 +2183,8 @@ __global__ __launch_bounds__(256) void k_t_cellcol(const unsigned *__restrict__ 
 
 // one workgroup: exclusive scan of the bins' (padded records << 32 | items)
 // -> bofs; the metadata the host reads: {nbad lo, nbad hi, gridded records,
-// items, first item of each first plane [nps + 1], padded records}
+// items, first item of each first plane [nps + 1], padded records, whether
+// the count pass dropped an in-grid visibility for its zero weight}
 __global__ __launch_bounds__(kTThreads) void k_t_binscan(
     int nb, int bins_per_plane, int nps, const unsigned long long *__restrict__ binsum,
     const unsigned *__restrict__ binbase, const unsigned long long *__restrict__ nbad,
@@ -2187,6 +2208,7 @@ __global__ __launch_bounds__(kTThreads) void k_t_binscan(
         meta[2] = binbase[nb];
         meta[3] = (unsigned)(t & 0xffffffffull);
         meta[5 + nps] = (unsigned)(t >> 32);
+        meta[6 + nps] = nbad[1] ? 1u : 0u;
     }
     for (int p = threadIdx.x; p <= nps; p += kTThreads)
         meta[4 + p] = (unsigned)((p < nps ? bofs[(size_t)p * bins_per_plane] : t) & 0xffffffffull);
@@ -3264,6 +3286,7 @@ struct Part {
     // host copies (read_part_meta)
     int64_t nrec = 0, nitems = 0;
     std::vector<unsigned> p0_items;
+    bool dropped = false;  // two-level count pass: in-grid visibilities of zero weight left out
     // two-level (tiled) plans: see k_t_count .. k_t_final_s
     int t_g1 = 0;          // workgroups of the count / value passes
     int64_t t_vpw = 0;     // visibilities per such workgroup
@@ -3523,6 +3546,122 @@ static Plan reuse_buckets(const Inputs &in) {
     return k.P;
 }
 
+// The bounds pass of a call that computes its own extremes: the 8 doubles of
+// k_bounds_final and the content fingerprint of uvw and freq riding on it
+// (one copy, one host sync).
+struct BoundsOut {
+    double b[8];
+    uint64_t fp[4];
+};
+
+static BoundsOut bounds_pass(const Inputs &in, hipStream_t st) {
+    auto *part = scratch<double>("bounds_part", 6 * kBoundsBlocks);
+    auto *fpart = scratch<unsigned long long>("bounds_fpart", 2 * kBoundsBlocks);
+    auto *bnd = scratch<double>("bounds", 12);  // 8 extremes, 4 fingerprint words
+    // (pinned [0, 64) and [64, ...) hold the plan's other reads)
+    double *hb = pinned_host<double>((size_t)1 << 19, 12);
+    const int nb =
+        (int)std::max<int64_t>(1, std::min<int64_t>(grid1d(in.nrow, 256), kBoundsBlocks));
+    const double su = (in.flags & SDP_HIP_FLIP_UW) ? -1.0 : 1.0;
+    k_bounds<<<nb, 256, 0, st>>>(in.uvw, in.uvw_rs, in.nrow, su, part, fpart);
+    k_bounds_final<<<1, 256, 0, st>>>(nb, part, fpart, in.freq, in.nchan, bnd,
+                                      reinterpret_cast<unsigned long long *>(bnd + 8));
+    SDP_HIP_CHECK(hipMemcpyAsync(hb, bnd, 12 * sizeof(double), hipMemcpyDeviceToHost, st));
+    SDP_HIP_CHECK(hipStreamSynchronize(st));
+    BoundsOut o;
+    std::memcpy(o.b, hb, sizeof o.b);
+    std::memcpy(o.fp, hb + 8, sizeof o.fp);
+    return o;
+}
+
+// The two-level sort's layout kept from one default invert to the next of
+// its (device, workspace slot): most of the sort -- the count pass, bins,
+// cell totals and bases, pads, work items -- is a function of uvw, freq and
+// the geometry alone, and those repeat (PSF and dirty image, Taylor moments,
+// major cycles, data / model / corrected columns).  The key is content, not
+// addresses: the fingerprint of the bounds pass, shapes, strides, geometry,
+// the flags that shape the plan, and every SDP_HIP_* environment knob (the
+// plan reads several; any change is a miss).  Kept only from a call whose
+// count pass dropped no in-grid visibility, so the layout is the x.all one
+// and holds for any later weights or flags; reuse classifies with x.all.
+// SDP_HIP_LAYOUT_CACHE=0 switches it off.
+struct LayoutKey {
+    uint64_t fp[4] = {0, 0, 0, 0}, env = 0;
+    int64_t uvw_rs = 0, nrow = 0;
+    int nchan = 0, nx = 0, ny = 0, do_w = 0;
+    double px = 0, py = 0, eps = 0;
+    unsigned flags = 0;  // FLIP_UW, FP32
+    bool operator==(const LayoutKey &o) const {
+        return std::memcmp(fp, o.fp, sizeof fp) == 0 && env == o.env && uvw_rs == o.uvw_rs &&
+               nrow == o.nrow && nchan == o.nchan && nx == o.nx && ny == o.ny && do_w == o.do_w &&
+               px == o.px && py == o.py && eps == o.eps && flags == o.flags;
+    }
+};
+
+struct KeptLayout {
+    bool valid = false;
+    uint64_t gen = 0;
+    LayoutKey key;
+    Plan P;
+};
+
+static std::map<int, KeptLayout> g_layout;  // [2 * device + slot], under g_kept_mu
+
+extern "C" char **environ;
+
+// order-independent hash of the SDP_HIP_* environment entries
+static uint64_t env_knobs_hash() {
+    uint64_t h = 0;
+    for (char **e = environ; e && *e; ++e) {
+        if (std::strncmp(*e, "SDP_HIP_", 8) != 0) continue;
+        uint64_t x = 0xcbf29ce484222325ull;
+        for (const char *c = *e; *c; ++c) x = (x ^ (unsigned char)*c) * 0x100000001b3ull;
+        h += fp_mix(x);
+    }
+    return h;
+}
+
+static LayoutKey layout_key(const Inputs &in, const BoundsOut &bo) {
+    LayoutKey k;
+    std::memcpy(k.fp, bo.fp, sizeof k.fp);
+    k.env = env_knobs_hash();
+    k.uvw_rs = in.uvw_rs;
+    k.nrow = in.nrow;
+    k.nchan = in.nchan;
+    k.nx = in.nx;
+    k.ny = in.ny;
+    k.do_w = in.do_w;
+    k.px = in.px;
+    k.py = in.py;
+    k.eps = in.eps;
+    k.flags = in.flags & (SDP_HIP_FLIP_UW | SDP_HIP_FP32);
+    return k;
+}
+
+// the slot's kept layout dropped: every fresh plan (it re-uses the slot's
+// bucketing scratch); a workspace release invalidates through the generation
+static void drop_kept_layout() {
+    std::lock_guard<std::mutex> lk(g_kept_mu);
+    g_layout[2 * cur_device() + ws_slot()].valid = false;
+}
+
+static bool find_kept_layout(const LayoutKey &key, Plan &P) {
+    std::lock_guard<std::mutex> lk(g_kept_mu);
+    const KeptLayout &k = g_layout[2 * cur_device() + ws_slot()];
+    if (!k.valid || k.gen != Workspace::get().generation() || !(k.key == key)) return false;
+    P = k.P;
+    return true;
+}
+
+static void keep_layout(const LayoutKey &key, const Plan &P) {
+    std::lock_guard<std::mutex> lk(g_kept_mu);
+    KeptLayout &k = g_layout[2 * cur_device() + ws_slot()];
+    k.valid = true;
+    k.gen = Workspace::get().generation();
+    k.key = key;
+    k.P = P;
+}
+
 static BatchSeq batch_token(const Plan &P, const Inputs &in) {
     BatchSeq s;
     s.valid = true;
@@ -3601,7 +3740,8 @@ static void geo_factors(Geo &g) {
 // Geometry shared by both directions: kernel, padded grid, w planes, bucket
 // granularity, row band, plane chunking.  One host sync (uvw and frequency
 // extremes) unless the bounds are given.
-static Plan plan_geometry_once(const Inputs &in, bool grid_mode, hipStream_t st, bool allow_fold) {
+static Plan plan_geometry_once(const Inputs &in, bool grid_mode, hipStream_t st, bool allow_fold,
+                               const BoundsOut *pre = nullptr) {
     SDP_REQUIRE(in.nx > 0 && in.ny > 0 && in.nx % 2 == 0 && in.ny % 2 == 0,
                 "npix_x and npix_y must be positive and even");
     SDP_REQUIRE(in.px > 0 && in.py > 0, "pixel sizes must be positive");
@@ -3611,11 +3751,12 @@ static Plan plan_geometry_once(const Inputs &in, bool grid_mode, hipStream_t st,
     // a fresh plan re-uses the bucketing scratch and may overwrite a batch
     // sequence's planes -- those of its own slot: kept buckets and batch
     // sequences exist in slot 0 only, and a slot-1 plan uses the '#1'
-    // buffers, so it leaves them valid
+    // buffers, so it leaves them valid; each slot has a kept layout
     if (ws_slot() == 0) {
         drop_kept_buckets();
         if (!in.bounds) drop_batch_seq();
     }
+    drop_kept_layout();
     Plan P;
     Geo &g = P.g;
     P.f64 = in.eps < 1.0e-7 && !(in.flags & SDP_HIP_FP32);
@@ -3654,15 +3795,10 @@ static Plan plan_geometry_once(const Inputs &in, bool grid_mode, hipStream_t st,
         hb[4] = b[4];
         hb[5] = b[5];
     } else {
-        auto *part = scratch<double>("bounds_part", 6 * kBoundsBlocks);
-        auto *bnd = scratch<double>("bounds", 8);
+        // (`pre`: the caller has run the pass already, for its fingerprint)
+        const BoundsOut bo = pre ? *pre : bounds_pass(in, st);
         hb = pinned_host<double>(0, 8);
-        const int nb = (int)std::max<int64_t>(
-            1, std::min<int64_t>(grid1d(in.nrow, 256), kBoundsBlocks));
-        k_bounds<<<nb, 256, 0, st>>>(in.uvw, in.uvw_rs, in.nrow, g.su, part);
-        k_bounds_final<<<1, 256, 0, st>>>(nb, part, in.freq, in.nchan, bnd);
-        SDP_HIP_CHECK(hipMemcpyAsync(hb, bnd, 8 * sizeof(double), hipMemcpyDeviceToHost, st));
-        SDP_HIP_CHECK(hipStreamSynchronize(st));
+        std::memcpy(hb, bo.b, sizeof bo.b);
         wf_lo = hb[6];
         wf_hi = hb[7];
     }
@@ -3942,9 +4078,11 @@ static Plan plan_geometry_once(const Inputs &in, bool grid_mode, hipStream_t st,
 // the result by the NUFFT's own approximation error (~2e-12: the mirrored w
 // sits at another offset between the planes).  Re-gridding every record once
 // per plane chunk dominates such a call anyway.
-static Plan plan_geometry(const Inputs &in, bool grid_mode, hipStream_t st) {
-    Plan P = plan_geometry_once(in, grid_mode, st, true);
-    if (P.g.fold && P.chunk_planes < P.g.nplanes) P = plan_geometry_once(in, grid_mode, st, false);
+static Plan plan_geometry(const Inputs &in, bool grid_mode, hipStream_t st,
+                          const BoundsOut *pre = nullptr) {
+    Plan P = plan_geometry_once(in, grid_mode, st, true, pre);
+    if (P.g.fold && P.chunk_planes < P.g.nplanes)
+        P = plan_geometry_once(in, grid_mode, st, false, pre);
     return P;
 }
 
@@ -4459,6 +4597,7 @@ static void fill_info(const Plan &P, sdp_hip_wgrid_info *info) {
     info->tiled = P.g.tiled;
     info->grid_launches = (P.g.nplanes + P.chunk_planes - 1) / P.chunk_planes;
     info->folded = P.g.fold;
+    info->layout_reused = 0;  // (ms2dirty sets it)
 }
 
 // Pruned 2-D FFT of each resident plane.  The uv grid is non-zero only in
@@ -4759,7 +4898,8 @@ static int cu_count() {
 // pads, work items and the move of every record to its cell.  The weight
 // sums go to `slots` (count pass; value pass when values_only).  values_only
 // (SDP_HIP_REUSE_BUCKETS): the kept plan's bins, chunks and cell bases are
-// valid, so only the value pass and the final move run.
+// valid, so only the value pass, the recount of the chunks' cells and the
+// final move run.
 static void bucket_tiled(Plan &P, const Inputs &in, bool grid_mode, hipStream_t st,
                          bool values_only, const std::function<void()> &after_clear,
                          double *slots) {
@@ -4802,11 +4942,11 @@ static void bucket_tiled(Plan &P, const Inputs &in, bool grid_mode, hipStream_t 
         pt.t_lkey = scratch<uint16_t>("rec_lkey", std::max<int64_t>(nvis, 1));
         pt.t_fsc = scratch<double>("t_fscale", g.nchan);
         pt.t_a = scratch<char>("recs_a", (size_t)std::max<int64_t>(nvis, 1) * rsz);
-        pt.nbad = scratch<unsigned long long>("nbad", 1);
-        pt.meta = scratch<unsigned>("meta", g.nps + 6);
+        pt.nbad = scratch<unsigned long long>("nbad", 2);  // {out of grid, dropped}
+        pt.meta = scratch<unsigned>("meta", g.nps + 7);
         SDP_HIP_CHECK(hipMemsetAsync(pt.t_binc, 0, nb * sizeof(unsigned), st));
         SDP_HIP_CHECK(hipMemsetAsync(pt.t_binsum, 0, nb * sizeof(unsigned long long), st));
-        SDP_HIP_CHECK(hipMemsetAsync(pt.nbad, 0, sizeof(unsigned long long), st));
+        SDP_HIP_CHECK(hipMemsetAsync(pt.nbad, 0, 2 * sizeof(unsigned long long), st));
         if (after_clear) after_clear();
     }
     k_fscale<<<grid1d(g.nchan, 256), 256, 0, st>>>(in.freq, g.nchan, pt.t_fsc);
@@ -4864,9 +5004,23 @@ static void bucket_tiled(Plan &P, const Inputs &in, bool grid_mode, hipStream_t 
         else staged(std::integral_constant<int, 1>{}, std::integral_constant<int, 2048>{});
         SDP_HIP_CHECK(hipGetLastError());
     };
+    const unsigned gseg =
+        (unsigned)std::min<int64_t>((int64_t)pt.t_maxseg * (kBinCells / 256), 8192);
+    const unsigned gcol = (unsigned)std::min<int64_t>((int64_t)nb * (kBinCells / 256), 8192);
     if (values_only) {
+        // The value pass ranks a record inside its workgroup's slice of a
+        // bin by LDS cursors its 8 waves race on, so where a slice straddles
+        // a chunk boundary the chunks' records -- and with them the per-chunk
+        // and per-segment cell counts the final move offsets by -- differ
+        // from the keeping call's.  They are counted again; the records of
+        // every bin and cell are the same set, so the bins, cell totals,
+        // cell bases, pads and work items hold.
         if (nvis > 0) {
             scatter(slots);
+            k_t_cellcount<<<gch, kTThreads, 0, st>>>(pt.t_chunks, pt.t_meta_ch, pt.t_lkey, pt.t_m2);
+            k_t_segscan<<<gseg, 256, 0, st>>>(pt.t_segs, pt.t_meta_ch, pt.t_m2, pt.t_stot);
+            k_t_cellcol<false><<<gcol, 256, 0, st>>>(pt.t_nbl, pt.t_segb, pt.t_nsegb, pt.t_stot,
+                                                     nullptr, P.chunk, nullptr);
             final_move();
         }
         return;
@@ -4882,10 +5036,7 @@ static void bucket_tiled(Plan &P, const Inputs &in, bool grid_mode, hipStream_t 
                                       pt.t_nbl, pt.t_chunks, pt.t_segs, pt.t_meta_ch);
     if (nvis > 0) scatter(nullptr);
     k_t_cellcount<<<gch, kTThreads, 0, st>>>(pt.t_chunks, pt.t_meta_ch, pt.t_lkey, pt.t_m2);
-    const unsigned gseg =
-        (unsigned)std::min<int64_t>((int64_t)pt.t_maxseg * (kBinCells / 256), 8192);
     k_t_segscan<<<gseg, 256, 0, st>>>(pt.t_segs, pt.t_meta_ch, pt.t_m2, pt.t_stot);
-    const unsigned gcol = (unsigned)std::min<int64_t>((int64_t)nb * (kBinCells / 256), 8192);
     if (P.pad4 || P.pad64)
         k_t_cellcol<true><<<gcol, 256, 0, st>>>(pt.t_nbl, pt.t_segb, pt.t_nsegb, pt.t_stot,
                                                 pt.t_tot, P.chunk, pt.t_binsum);
@@ -4899,7 +5050,7 @@ static void bucket_tiled(Plan &P, const Inputs &in, bool grid_mode, hipStream_t 
     // the metadata (one sync): out-of-grid check, record / item counts, the
     // first item of each first plane, the padded record total
     const int nps = g.nps;
-    const size_t per = (size_t)nps + 6;
+    const size_t per = (size_t)nps + 7;
     unsigned *m = pinned_host<unsigned>(64, per);
     SDP_HIP_CHECK(hipMemcpyAsync(m, pt.meta, per * sizeof(unsigned), hipMemcpyDeviceToHost, st));
     SDP_HIP_CHECK(hipStreamSynchronize(st));
@@ -4911,6 +5062,7 @@ static void bucket_tiled(Plan &P, const Inputs &in, bool grid_mode, hipStream_t 
     pt.nitems = m[3];
     pt.p0_items.assign(m + 4, m + 4 + nps + 1);
     const size_t ntot = (size_t)m[5 + nps];
+    pt.dropped = m[6 + nps] != 0;
     P.recs = reinterpret_cast<VisRec *>(scratch<char>("recs", (ntot + 1) * rsz));
     pt.fitems = scratch<FineItem>("fitems", (size_t)pt.nitems + 1);
     const unsigned gfin = (unsigned)std::min(nb, 4096);
@@ -5168,7 +5320,32 @@ static void ms2dirty(const Inputs &in, double *dirty, int64_t sx, int64_t sy,
     // zeros); its reuse classifies them the same way (the two-level value
     // pass re-derives the bin ranks from that classification)
     inx.x.all = keep || reuse;
-    Plan P = reuse ? reuse_buckets(in) : plan_geometry(inx, true, st);
+    // a default invert (no flag that shares or splits a bucketing) looks its
+    // uvw, freq and geometry up in the slot's kept layout: the bounds pass
+    // first (it carries the fingerprint), then either the kept plan with a
+    // value-only bucketing, or a fresh plan from the same bounds
+    const bool cacheable = !keep && !reuse && !in.bounds && !(in.flags & SDP_HIP_W_SLAB) &&
+                           !(in.eps < 1.0e-7 && !(in.flags & SDP_HIP_FP32)) && in.nrow > 0 &&
+                           env_int("SDP_HIP_LAYOUT_CACHE", 1) != 0;
+    BoundsOut bo;
+    LayoutKey lkey;
+    bool hit = false;
+    Plan P;
+    if (cacheable) {
+        bo = bounds_pass(in, st);
+        lkey = layout_key(in, bo);
+        hit = find_kept_layout(lkey, P);
+    }
+    if (hit) {
+        // (the slot's record scratch and planes are overwritten, as by a fresh plan)
+        if (ws_slot() == 0) {
+            drop_kept_buckets();
+            drop_batch_seq();
+        }
+        inx.x.all = true;
+    } else {
+        P = reuse ? reuse_buckets(in) : plan_geometry(inx, true, st, cacheable ? &bo : nullptr);
+    }
     setup_core(P);
     const Geo &g = P.g;
     // batched invert: planes zeroed by the first batch, FFT + screens by the
@@ -5187,7 +5364,7 @@ static void ms2dirty(const Inputs &in, double *dirty, int64_t sx, int64_t sy,
     auto start_zero = [&] {
         if (first && !batched) zero_first_band(aux, P);
     };
-    if (reuse) {
+    if (reuse || hit) {
         start_zero();
         // value pass only (weight sums included)
         double *slots = in.x.sumwt ? scratch<double>("sumwt_slots", kSumSlots) : nullptr;
@@ -5200,11 +5377,15 @@ static void ms2dirty(const Inputs &in, double *dirty, int64_t sx, int64_t sy,
     }
     if (P.subsort) subsort_items(P, st);
     if (keep) keep_buckets(P, in);
+    // (fp32 two-level plans on padded cells; a layout that left a zero-weight
+    // visibility out is not the x.all one)
+    if (cacheable && !hit && P.g.tiled && !P.f64 && P.pad4 && !P.pt.dropped) keep_layout(lkey, P);
     StageMs ms;
     invert_planes(P, dirty, sx, sy, (in.flags & SDP_HIP_ACCUMULATE) ? 1 : 0, first, last, tab, aux,
                   ms, st);
     if (batched && last) drop_batch_seq();
     finish_info(P, tm, ms, info);
+    if (info) info->layout_reused = hit ? 1 : 0;
 }
 
 // image pol q of a pols call as a conversion: row q of the matrix, pol q's flags
@@ -5599,6 +5780,17 @@ int sdp_hip_wstack_layout(const double *bounds, int npix_x, int npix_y, double p
         info->w0 = g.w0;
         info->dw = g.dw;
         info->fp64 = f64 ? 1 : 0;
+    });
+}
+
+int sdp_hip_wstack_fingerprint(const double *uvw, int64_t uvw_row_stride, int64_t nrow,
+                               const double *freq, int nchan, uint64_t *out, char *errbuf,
+                               size_t errbuf_len) {
+    return guarded(errbuf, errbuf_len, [&] {
+        SDP_REQUIRE(out != nullptr && (uvw != nullptr || nrow <= 0) &&
+                        (freq != nullptr || nchan <= 0),
+                    "null pointer argument");
+        wstack::fingerprint_host(uvw, uvw_row_stride, nrow, freq, nchan, out);
     });
 }
 

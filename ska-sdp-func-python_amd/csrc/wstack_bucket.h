@@ -20,6 +20,7 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "wstack_fingerprint.h"
 #include "wstack_types.h"
 
 namespace sdp {
@@ -33,15 +34,21 @@ constexpr int kBoundsBlocks = 1024;
 
 // raw extremes in metres (min/max of su*w, max |u|, max |v|, and min/max of
 // the Hermitian-folded su*w: negated on the rows with su*u < 0); the host
-// scales them by the frequency range (w*s is monotonic in w for s > 0)
+// scales them by the frequency range (w*s is monotonic in w for s > 0).
+// fpart: the block's two fingerprint words of its rows (wstack_fingerprint.h;
+// wrapping sums, so the grid-stride order does not matter)
 __global__ __launch_bounds__(256) void k_bounds(const double *__restrict__ uvw, int64_t rs,
                                                 int64_t nrow, double su,
-                                                double *__restrict__ part) {
+                                                double *__restrict__ part,
+                                                unsigned long long *__restrict__ fpart) {
     __shared__ double red[6][4];
+    __shared__ unsigned long long fred[2][4];
     double wmn = 1e300, wmx = -1e300, umx = 0.0, vmx = 0.0, fmn = 1e300, fmx = -1e300;
+    uint64_t fa = 0, fb = 0;
     for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < nrow;
          r += (int64_t)gridDim.x * blockDim.x) {
-        const double u = uvw[r * rs], v = uvw[r * rs + 1], w = su * uvw[r * rs + 2];
+        const double u = uvw[r * rs], v = uvw[r * rs + 1], wr = uvw[r * rs + 2], w = su * wr;
+        fp_add_row((uint64_t)r, u, v, wr, fa, fb);
         wmn = fmin(wmn, w);
         wmx = fmax(wmx, w);
         umx = fmax(umx, fabs(u));
@@ -57,9 +64,13 @@ __global__ __launch_bounds__(256) void k_bounds(const double *__restrict__ uvw, 
         vmx = fmax(vmx, __shfl_xor(vmx, o));
         fmn = fmin(fmn, __shfl_xor(fmn, o));
         fmx = fmax(fmx, __shfl_xor(fmx, o));
+        fa += (uint64_t)__shfl_xor((unsigned long long)fa, o);
+        fb += (uint64_t)__shfl_xor((unsigned long long)fb, o);
     }
     const int wv = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
+        fred[0][wv] = fa;
+        fred[1][wv] = fb;
         red[0][wv] = wmn;
         red[1][wv] = wmx;
         red[2][wv] = umx;
@@ -78,16 +89,23 @@ __global__ __launch_bounds__(256) void k_bounds(const double *__restrict__ uvw, 
             red[5][0] = fmax(red[5][0], red[5][k]);
         }
         for (int k = 0; k < 6; ++k) part[k * kBoundsBlocks + blockIdx.x] = red[k][0];
+        for (int k = 0; k < 2; ++k)
+            fpart[k * kBoundsBlocks + blockIdx.x] = fred[k][0] + fred[k][1] + fred[k][2] + fred[k][3];
     }
 }
 
 // out = {min su*w, max su*w, max|u|, max|v|, min freq, max freq, min and max
-// of the folded su*w}
+// of the folded su*w}; fout = the content fingerprint {uvw a, uvw b, freq a,
+// freq b} (fingerprint_host computes the same on the host)
 __global__ __launch_bounds__(256) void k_bounds_final(int nblocks, const double *__restrict__ part,
+                                                      const unsigned long long *__restrict__ fpart,
                                                       const double *__restrict__ freq, int nchan,
-                                                      double *__restrict__ out) {
+                                                      double *__restrict__ out,
+                                                      unsigned long long *__restrict__ fout) {
     __shared__ double red[8][256];
+    __shared__ unsigned long long fred[4][4];
     double a[8] = {1e300, -1e300, 0.0, 0.0, 1e300, -1e300, 1e300, -1e300};
+    uint64_t f[4] = {0, 0, 0, 0};
     for (int b = threadIdx.x; b < nblocks; b += 256) {
         a[0] = fmin(a[0], part[b]);
         a[1] = fmax(a[1], part[kBoundsBlocks + b]);
@@ -95,13 +113,23 @@ __global__ __launch_bounds__(256) void k_bounds_final(int nblocks, const double 
         a[3] = fmax(a[3], part[3 * kBoundsBlocks + b]);
         a[6] = fmin(a[6], part[4 * kBoundsBlocks + b]);
         a[7] = fmax(a[7], part[5 * kBoundsBlocks + b]);
+        f[0] += fpart[b];
+        f[1] += fpart[kBoundsBlocks + b];
     }
     for (int c = threadIdx.x; c < nchan; c += 256) {
         a[4] = fmin(a[4], freq[c]);
         a[5] = fmax(a[5], freq[c]);
+        fp_add_freq((uint64_t)c, freq[c], f[2], f[3]);
+    }
+    for (int k = 0; k < 4; ++k) {
+        for (int o = 32; o > 0; o >>= 1) f[k] += (uint64_t)__shfl_xor((unsigned long long)f[k], o);
+        if ((threadIdx.x & 63) == 0) fred[k][threadIdx.x >> 6] = f[k];
     }
     for (int k = 0; k < 8; ++k) red[k][threadIdx.x] = a[k];
     __syncthreads();
+    if (threadIdx.x < 4)
+        fout[threadIdx.x] = fred[threadIdx.x][0] + fred[threadIdx.x][1] + fred[threadIdx.x][2] +
+                            fred[threadIdx.x][3];
     for (int st = 128; st > 0; st >>= 1) {
         if (threadIdx.x < st) {
             const int t = threadIdx.x;

@@ -86,6 +86,7 @@ class WGridInfo(ctypes.Structure):
         ("fp64", c_int),
         ("tiled", c_int),
         ("folded", c_int),
+        ("layout_reused", c_int),
     ]
 
     def as_dict(self):
@@ -117,6 +118,7 @@ SIGNATURES = {
     "sdp_hip_wstack_layout": [
         c_vp, c_int, c_int, c_dbl, c_dbl, c_dbl, c_int, c_u32,  # bounds, geometry, eps, do_w, flags
         ctypes.POINTER(WGridInfo)] + _ERR,
+    "sdp_hip_wstack_fingerprint": [c_vp, c_i64, c_i64, c_vp, c_int, c_vp] + _ERR,
     "sdp_hip_ms2dirty_vis": [
         c_vp, c_i64, c_vp, c_int, c_i64,          # uvw, stride, freq, nchan, nrow
         c_vp, c_int, c_i64, c_i64, c_i64, c_int,  # vis, dtype, row/chan/pol strides, npol_vis

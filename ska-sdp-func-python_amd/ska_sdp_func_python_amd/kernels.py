@@ -133,6 +133,11 @@ def ms2dirty(uvw, freq, vis, wgt, npix_x, npix_y, pixsize_x, pixsize_y,
     ``out_strides`` = (stride_x, stride_y) in elements) and an info dict.
     ``slot=1`` uses the library's second scratch set (SDP_HIP_SLOT1): calls
     alternated between two streams and slots overlap on the device.
+
+    ``info["layout_reused"]`` is 1 when the call found the bucketing layout
+    its slot kept from the previous invert of the same uvw, freq (by content)
+    and geometry, and ran only the value passes of the sort
+    (``SDP_HIP_LAYOUT_CACHE=0`` switches the cache off).
     """
     pbits = _prec_bits(epsilon, precision)
     _check_uvw(uvw)
@@ -199,6 +204,26 @@ def wstack_layout(bounds, npix_x, npix_y, pixsize_x, pixsize_y, epsilon=1e-7, do
     d = info.as_dict()
     d["nps"] = d["nplanes"] - d["support"] + 1 if d["nplanes"] > 1 else 1
     return d
+
+
+def layout_fingerprint(uvw, freq):
+    """The content fingerprint an invert keeps its bucketing layout under
+    (``info["layout_reused"]``), computed on the host from HOST arrays ``uvw``
+    [nrow, 3] and ``freq`` [nchan] (sdp_hip_wstack_fingerprint, no device
+    work): four 64-bit words {uvw a, uvw b, freq a, freq b}."""
+    import numpy as np
+    uvw = np.asarray(uvw, dtype=np.float64)
+    freq = np.ascontiguousarray(freq, dtype=np.float64)
+    if uvw.ndim != 2 or uvw.shape[1] != 3 or freq.ndim != 1:
+        raise ValueError("uvw must be [nrow, 3] and freq [nchan]")
+    # (rows with a stride are read in place, as the device arrays are)
+    if uvw.strides[1] != 8 or uvw.strides[0] % 8 or uvw.strides[0] < 24:
+        uvw = np.ascontiguousarray(uvw)
+    out = (ctypes.c_uint64 * 4)()
+    _lib.call("sdp_hip_wstack_fingerprint", ctypes.c_void_p(uvw.ctypes.data),
+              uvw.strides[0] // 8, uvw.shape[0],
+              ctypes.c_void_p(freq.ctypes.data), freq.shape[0], ctypes.cast(out, ctypes.c_void_p))
+    return tuple(int(x) for x in out)
 
 
 def ms2dirty_batch(uvw, freq, vis, wgt, npix_x, npix_y, pixsize_x, pixsize_y, bounds,
