@@ -17,8 +17,11 @@
 //   bounds_pass        a default invert: k_bounds first, for the content
 //                      fingerprint (wstack_fingerprint.h) of uvw and freq;
 //                      the slot's kept layout (KeptLayout) with that key
-//                      replaces plan_geometry, and bucket_tiled runs
-//                      values_only
+//                      replaces plan_geometry, and bucket_tiled replays the
+//                      permutation the keeping call recorded: k_t_values
+//                      (8-byte values to their kept positions), k_t_replay
+//                      (the final move of the values alone; the records'
+//                      offsets stay in place)
 //   plan_geometry      k_bounds: w range and uv extent; support, padded
 //                      grid, plane layout, Hermitian fold, bucket window,
 //                      bucketing route, Plan flags, resident planes
@@ -27,7 +30,8 @@
 //                      routes below; subsort_items on the coarse route
 //   per chunk of resident planes (invert_planes):
 //     zero_band
-//     grid_f32         k_grid_mfma_pad (Plan::pad4 or Plan::subpad)
+//     grid_f32         k_grid_mfma_pad (Plan::pad4 or Plan::subpad), on the
+//                      two-level sort's split records k_grid_mfma_pad_soa
 //     grid_f64         k_grid_f64_mfma (Plan::pad64) or k_grid_f64
 //     core_merge       fp32: the fp64 uv core into the planes
 //     fft_rows_y       hipFFT over the band rows
@@ -691,12 +695,38 @@ __device__ __forceinline__ void region_flush(const Geo &g, const float *reg, int
     }
 }
 
-template <int W, bool WS, int NG>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_grid_mfma_pad(
-    Geo g, const RecC *__restrict__ recs, const FineItem *__restrict__ items, uint32_t n_items,
-    float *__restrict__ grid, int p_lo, int p_hi, CoreAcc core) {
+// The gridder's body.  SOA: the records come as two arrays -- `recs` is the
+// values (float2) and `offs` the packed offsets (the two-level sort's final
+// layout) -- and a lane loads its record as two 8-byte loads; else `recs` is
+// RecC and `offs` unused.
+template <int W, bool WS, int NG, bool SOA>
+__device__ __forceinline__ void grid_mfma_pad_body(
+    const Geo &g, const RecC *__restrict__ recs_, const uint2 *__restrict__ offs,
+    const FineItem *__restrict__ items, uint32_t n_items, float *__restrict__ grid, int p_lo,
+    int p_hi, const CoreAcc &core) {
     static_assert(W <= 8, "the MFMA tiles hold 8 taps per axis");
     static_assert(NG == 1 || NG == 2 || NG == 4 || NG == 8 || NG == 16, "units of 1-16 groups");
+    static_assert(!SOA || NG == 1, "the split layout is the one-cell plans'");
+    // recs[i]: record i in either layout
+    struct RecSrc {
+        const RecC *__restrict__ r;
+        const uint2 *__restrict__ o;
+        __device__ __forceinline__ RecC operator[](uint32_t i) const {
+            if constexpr (SOA) {
+                const float2 v = reinterpret_cast<const float2 *>(r)[i];
+                const uint2 q = o[i];
+                RecC rc;
+                rc.cre = v.x;
+                rc.cim = v.y;
+                rc.lo = q.x;
+                rc.hi = q.y;
+                return rc;
+            } else {
+                return r[i];
+            }
+        }
+    };
+    const RecSrc recs{recs_, offs};
     // (NG = 2, 8, 16 are valid but measured slower on C4; only 1 and 4 are launched)
     extern __shared__ __attribute__((aligned(16))) float2 tile[];
     constexpr int kRegX = PadUnit<NG>::RGX, kRegY = PadUnit<NG>::RGY;
@@ -890,6 +920,23 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4))) void
 
         region_flush<W, WS, NG>(g, reg, ibase, jbase, p0, p_lo, p_hi, core, grid, lane, 0, 1);
     }
+}
+
+template <int W, bool WS, int NG>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4))) void k_grid_mfma_pad(
+    Geo g, const RecC *__restrict__ recs, const FineItem *__restrict__ items, uint32_t n_items,
+    float *__restrict__ grid, int p_lo, int p_hi, CoreAcc core) {
+    grid_mfma_pad_body<W, WS, NG, false>(g, recs, nullptr, items, n_items, grid, p_lo, p_hi, core);
+}
+
+// ... on the two-level sort's split records (NG = 1 only: the tiled plans)
+template <int W, bool WS>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4))) void
+k_grid_mfma_pad_soa(Geo g, const float2 *__restrict__ vals, const uint2 *__restrict__ offs,
+                    const FineItem *__restrict__ items, uint32_t n_items, float *__restrict__ grid,
+                    int p_lo, int p_hi, CoreAcc core) {
+    grid_mfma_pad_body<W, WS, 1, true>(g, reinterpret_cast<const RecC *>(vals), offs, items,
+                                       n_items, grid, p_lo, p_hi, core);
 }
 
 // MFMA degridder (predict) on one-cell buckets: the adjoint of
@@ -1717,7 +1764,14 @@ __global__ void k_bucket_f64(Geo g, int64_t nvis, const double *__restrict__ uvw
 //                 metadata the host reads (the only host sync)
 //   k_t_cellfin   per bin: cell bases, pad records, FineItem work items
 //   k_t_final_s   per chunk: records moved to their cell (LDS cursors
-//                 seeded with the cell base + the chunk's prefix)
+//                 seeded with the cell base + the chunk's prefix); the fp32
+//                 invert's RecC records leave as two arrays, values and
+//                 offsets
+// A hit on a kept layout (KeptLayout) runs two kernels instead:
+//   k_t_values    the visibility's 8-byte value to the position the keeping
+//                 call's value pass gave it (t_pos)
+//   k_t_replay    the values staged and moved as the keeping call's final
+//                 move did (t_slot, t_dst); the offsets stay where they are
 // The writes of the two scatter passes land in runs inside the few bins /
 // cells a workgroup touches at a time, not at random addresses.
 constexpr int kMaxBins = 16384;    // LDS histogram of the first level (64 KiB)
@@ -1730,6 +1784,11 @@ constexpr unsigned kTSeg = 16;       // chunks per segment of the cells' column 
 constexpr int kTU = 1;
 constexpr int kTUc = 2;  // the same for the count pass (C2: 0.66 ms, 0.69 for 4)
 constexpr int kTU2 = 4;              // records per lane in flight (cell count / final move)
+// records per LDS-staged batch of the fp32 invert's final move (RecC); a kept
+// layout's staging slots are relative to these batches, so k_t_replay's own
+// batch is a multiple of it (SDP_HIP_TREPLAY_NB: 4096, or 8192 -- at 8 B per
+// record the staging LDS the 16-byte move has)
+constexpr int kTFinalNB = 4096;
 
 struct TChunk {
     uint32_t bin, b, e, seg;  // records [b, e) of `bin`; `seg`: its prefix segment
@@ -1948,18 +2007,46 @@ struct TRec<3> {
     using type = Rec64;
 };
 
+// the phase (turns) a record's value is rotated by: the w screen's at the
+// original w (cw = Coord::w = su w_m s) plus the phase shift's
+__device__ __forceinline__ double t_phase(const Geo &g, const VisExtra &x, const TLoad &L,
+                                          double cw) {
+    double ph = g.do_w ? cw * g.s0 : 0.0;
+    if (x.shift) ph += (L.um * x.sl + L.vm * x.sm + L.wm * x.sn) * L.s;
+    return ph - rint(ph);
+}
+
+// The fp32 value of a record (RecC, VisRec): weight (x visibility), rotated
+// by `ph`, then conjugated by the fold -- the one place it is computed, for
+// the value pass's records (t_write) and a kept layout's hits (k_t_values)
+template <bool kGrid>
+__device__ __forceinline__ float2 t_value_f32(double wd, float2 xv, bool rot, double ph,
+                                              bool conj) {
+    const float wt = (float)wd;
+    float cr = wt, ci = 0.0f;
+    if (kGrid) {
+        cr = wt != 0.0f ? xv.x * wt : 0.0f;
+        ci = wt != 0.0f ? xv.y * wt : 0.0f;
+    }
+    if (rot) {
+        float sn, cs;
+        sincospif((float)(2.0 * ph), &sn, &cs);
+        if (!kGrid) sn = -sn;
+        const float r_ = cr * cs - ci * sn, i_ = cr * sn + ci * cs;
+        cr = r_;
+        ci = i_;
+    }
+    if (kGrid && conj) ci = -ci;  // (folded: after the rotation)
+    return make_float2(cr, ci);
+}
+
 // Record writers of the value pass: the fields bucket_one / k_bucket_f64
 // write for the single-level path, computed the same way.
 template <int KIND, bool kGrid, class XV>
 __device__ __forceinline__ void t_write(const Geo &g, const VisExtra &x, const TLoad &L,
                                         const TPoint &p, XV xv, void *out, unsigned pos) {
-    double ph = 0.0;
     const bool rot = g.do_w || x.shift;
-    if (rot) {
-        ph = g.do_w ? p.c.w * g.s0 : 0.0;
-        if (x.shift) ph += (L.um * x.sl + L.vm * x.sm + L.wm * x.sn) * L.s;
-        ph -= rint(ph);
-    }
+    const double ph = rot ? t_phase(g, x, L, p.c.w) : 0.0;
     if constexpr (KIND >= 2) {
         double cr = p.wd, ci = 0.0;
         if (kGrid) {
@@ -1985,21 +2072,9 @@ __device__ __forceinline__ void t_write(const Geo &g, const VisExtra &x, const T
         rec.pad = 0u;
         static_cast<Rec64 *>(out)[pos] = rec;
     } else {
-        const float wt = (float)p.wd;
-        float cr = wt, ci = 0.0f;
-        if (kGrid) {
-            cr = wt != 0.0f ? xv.x * wt : 0.0f;
-            ci = wt != 0.0f ? xv.y * wt : 0.0f;
-        }
-        if (rot) {
-            float sn, cs;
-            sincospif((float)(2.0 * ph), &sn, &cs);
-            if (!kGrid) sn = -sn;
-            const float r_ = cr * cs - ci * sn, i_ = cr * sn + ci * cs;
-            cr = r_;
-            ci = i_;
-        }
-        if (kGrid && p.c.conj) ci = -ci;  // (folded: after the rotation)
+        const float2 val =
+            t_value_f32<kGrid>(p.wd, make_float2(xv.x, xv.y), rot, ph, p.c.conj);
+        const float cr = val.x, ci = val.y;
         if constexpr (KIND == 0) {
             const double base = 1.0 - 0.5 * g.W;
             const uint32_t qu = fix_frac(base - p.c.du, 21), qv = fix_frac(base - p.c.dv, 21);
@@ -2031,7 +2106,7 @@ __global__ __launch_bounds__(kT1Threads) void k_t_scatter(
     const double *__restrict__ fsc, const VT *__restrict__ vis, int64_t vrs, int64_t vcs,
     const void *__restrict__ wgt, int64_t wrs, int64_t wcs, VisExtra x, double *sw_slots,
     const unsigned *__restrict__ binbase, const unsigned *__restrict__ m1, void *__restrict__ out,
-    uint16_t *__restrict__ lkey) {
+    uint16_t *__restrict__ lkey, unsigned *__restrict__ vpos) {
     using V = TVal<VT, KIND, kGrid, FB>;
     extern __shared__ unsigned cur[];
     const int nb = g.nbins;
@@ -2059,6 +2134,51 @@ __global__ __launch_bounds__(kT1Threads) void k_t_scatter(
             if (p.in) {
                 t_write<KIND, kGrid>(g, x, L[u], p, xv, out, pos);
                 lkey[pos] = (uint16_t)(key & (kBinCells - 1));
+            }
+            // a call that may keep its layout: the visibility's position, for
+            // the hits' value pass (none: a visibility this call left out)
+            if (vpos && L[u].live)
+                vpos[base + u * kT1Threads + threadIdx.x] = p.in ? pos : 0xffffffffu;
+        }
+    }
+    if (sw_slots) t_weight_sum(ws, sw_slots);
+}
+
+// The value pass of a kept layout's hit: the visibility's value (loaded,
+// weighted, rotated and conjugated as k_t_scatter's t_write does) stored at
+// the position the keeping call gave it.  No classification, no cursors: the
+// position, and behind it the record's offsets and cell, are functions of
+// uvw, freq and the geometry, which the layout's key pins.  `nrec` bounds the
+// positions.
+template <class VT, int WT, int FB>
+__global__ __launch_bounds__(kT1Threads) void k_t_values(
+    Geo g, int64_t nvis, int64_t vpw, const double *__restrict__ uvw, int64_t rs,
+    const double *__restrict__ fsc, const VT *__restrict__ vis, int64_t vrs, int64_t vcs,
+    const void *__restrict__ wgt, int64_t wrs, int64_t wcs, VisExtra x, double *sw_slots,
+    const unsigned *__restrict__ vpos, unsigned nrec, float2 *__restrict__ out) {
+    using V = TVal<VT, 0, true, FB>;
+    const int64_t v0 = (int64_t)blockIdx.x * vpw, v1 = min(nvis, v0 + vpw);
+    const bool rot = g.do_w || x.shift;
+    double ws = 0.0;
+    for (int64_t base = v0; base < v1; base += (int64_t)kT1Threads * kTU) {
+        TLoad L[kTU];
+        VT raw[kTU];
+        unsigned pos[kTU];
+#pragma unroll
+        for (int u = 0; u < kTU; ++u) {
+            const int64_t v = base + u * kT1Threads + threadIdx.x;
+            L[u] = t_load<WT, FB>(g, v, v1, uvw, rs, fsc, wgt, wrs, wcs, x);
+            raw[u] = V::load(vis, vrs, vcs, x, L[u]);
+            pos[u] = vpos[min(v, v1 - 1)];
+        }
+#pragma unroll
+        for (int u = 0; u < kTU; ++u) {
+            const float2 xv = V::value(vis, vrs, vcs, x, L[u], raw[u]);
+            ws += L[u].wd;
+            if (L[u].live && pos[u] < nrec) {
+                const double ph = rot ? t_phase(g, x, L[u], g.su * (L[u].wm * L[u].s)) : 0.0;
+                out[pos[u]] = t_value_f32<true>(L[u].wd, xv, rot, ph,
+                                                g.fold && g.su * L[u].um < 0.0);
             }
         }
     }
@@ -2216,14 +2336,16 @@ __global__ __launch_bounds__(kTThreads) void k_t_binscan(
 
 // per non-empty bin, thread = one of its 256 groups of 16 cells: cell bases
 // (cbase, absolute record index), zero pad records behind each cell's
-// records (RecC, PAD), and the group's FineItems (chunks of `chunk` padded
-// records, each with the 16 cell ends)
+// records (PAD; KIND 0: RecC's halves into `recs` = values and `offs`), and
+// the group's FineItems (chunks of `chunk` padded records, each with the 16
+// cell ends)
 template <bool PAD, int KIND>
 __global__ __launch_bounds__(256) void k_t_cellfin(const Geo g, const unsigned *__restrict__ nbl,
                                                    const unsigned *__restrict__ tot,
                                                    const unsigned long long *__restrict__ bofs,
                                                    unsigned chunk, unsigned *__restrict__ cbase,
                                                    void *__restrict__ recs,
+                                                   uint2 *__restrict__ offs,
                                                    FineItem *__restrict__ items) {
     __shared__ typename hipcub::BlockScan<unsigned long long, 256>::TempStorage tmp;
     const unsigned nne = nbl[0];
@@ -2268,10 +2390,16 @@ __global__ __launch_bounds__(256) void k_t_cellfin(const Geo g, const unsigned *
                     z.idx = z.pad = 0u;
                     for (unsigned i = run + n[j]; i < run + r; ++i) static_cast<Rec64 *>(recs)[i] = z;
                 } else {
-                    RecC z;
-                    z.cre = z.cim = 0.0f;
-                    z.lo = z.hi = 0u;
-                    for (unsigned i = run + n[j]; i < run + r; ++i) static_cast<RecC *>(recs)[i] = z;
+                    // (split records: RecC's halves, the values and the offsets,
+                    // one array each)
+                    for (unsigned i = run + n[j]; i < run + r; ++i) {
+                        if (offs) {
+                            static_cast<float2 *>(recs)[i] = make_float2(0.0f, 0.0f);
+                            offs[i] = make_uint2(0u, 0u);
+                        } else {
+                            static_cast<uint4 *>(recs)[i] = make_uint4(0u, 0u, 0u, 0u);
+                        }
+                    }
                 }
             }
             run += r;
@@ -2297,6 +2425,10 @@ __global__ __launch_bounds__(256) void k_t_cellfin(const Geo g, const unsigned *
 // written out in that order, so a cell's records of the batch leave as one
 // contiguous run instead of lane-scattered 16-byte stores.  LDS: cursors and
 // batch counts (kBinCells each), the staged records and their destinations.
+// KIND 0 (RecC): a staged record leaves as its two halves, the value to `out`
+// and the offsets to `offs`; with slot_out / dst_out (a call that may keep its
+// layout) every record's staging slot and every slot's destination are
+// written too, for k_t_replay.
 template <int KIND, int NB>
 constexpr size_t t_final_lds() {
     return (size_t)2 * kBinCells * sizeof(unsigned) + (size_t)NB * sizeof(unsigned) +
@@ -2311,7 +2443,10 @@ __global__ __launch_bounds__(kTThreads) void k_t_final_s(const TChunk *__restric
                                                          const unsigned *__restrict__ stot,
                                                          const unsigned *__restrict__ cbase,
                                                          const void *__restrict__ in,
-                                                         void *__restrict__ out, int xmap) {
+                                                         void *__restrict__ out, int xmap,
+                                                         uint2 *__restrict__ offs,
+                                                         uint16_t *__restrict__ slot_out,
+                                                         unsigned *__restrict__ dst_out) {
     using R = typename TRec<KIND>::type;
     constexpr int NW = (int)(sizeof(R) / sizeof(uint4));
     constexpr int U = NB / kTThreads;
@@ -2390,6 +2525,8 @@ __global__ __launch_bounds__(kTThreads) void k_t_final_s(const TChunk *__restric
                 if (k[u] != 0xffffu) {
                     const unsigned slot = cnt[k[u]] + rk[u];
                     sdst[slot] = cur[k[u]] + rk[u];
+                    if (KIND == 0 && slot_out)
+                        slot_out[i0 + u * kTThreads + threadIdx.x] = (uint16_t)slot;
 #pragma unroll
                     for (int q = 0; q < NW; ++q)
                         stg[slot * NW + q] =
@@ -2398,14 +2535,83 @@ __global__ __launch_bounds__(kTThreads) void k_t_final_s(const TChunk *__restric
             }
             __syncthreads();
             const int nb = (int)min((uint32_t)NB, t.e - i0);
-            for (int j = threadIdx.x; j < nb * NW; j += kTThreads) {
-                const int rec = j / NW, q = j - rec * NW;
-                dst[(size_t)sdst[rec] * NW + q] = stg[j];
+            if constexpr (KIND == 0) {
+                // RecC's halves to the value and the offset array; a call that
+                // may keep its layout records where each staged record went
+                float2 *const vals = static_cast<float2 *>(out);
+                for (int j = threadIdx.x; j < nb; j += kTThreads) {
+                    const uint4 v = stg[j];
+                    const unsigned d = sdst[j];
+                    if (offs) {
+                        vals[d] = make_float2(__uint_as_float(v.x), __uint_as_float(v.y));
+                        offs[d] = make_uint2(v.z, v.w);
+                    } else {
+                        dst[d] = v;
+                    }
+                    if (dst_out) dst_out[i0 + j] = d;
+                }
+            } else {
+                for (int j = threadIdx.x; j < nb * NW; j += kTThreads) {
+                    const int rec = j / NW, q = j - rec * NW;
+                    dst[(size_t)sdst[rec] * NW + q] = stg[j];
+                }
             }
 #pragma unroll
             for (int j = 0; j < CPT; ++j) {
                 cur[c0 + j] += h[j];
                 cnt[c0 + j] = 0u;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// k_t_replay, the final move of a kept layout's hit.  The keeping call's
+// k_t_final_s<0, kTFinalNB> ranked the records of a batch on LDS counters its
+// waves race on, so which of a cell's slots a record got is that call's; the
+// offsets went there with it (offs) and stay.  It recorded, per t_a record,
+// the staging slot in its batch (slot) and, per staged record, the final
+// position (dstp); here the batch's 8-byte values are staged by those slots
+// and leave in the same per-cell runs.  No keys, cursors, histogram or scan.
+// NB: a multiple of kTFinalNB (batches start at the chunk's first record).
+// `ntot` bounds the positions.
+template <int NB>
+__global__ __launch_bounds__(kTThreads) void k_t_replay(const TChunk *__restrict__ chunks,
+                                                        const unsigned *__restrict__ meta_ch,
+                                                        const uint16_t *__restrict__ slot,
+                                                        const unsigned *__restrict__ dstp,
+                                                        const float2 *__restrict__ in,
+                                                        float2 *__restrict__ vals, unsigned ntot,
+                                                        int xmap, int stride) {
+    constexpr int U = NB / kTThreads;
+    static_assert(NB % kTFinalNB == 0 && kTFinalNB % kTThreads == 0, "k_t_replay batch shape");
+    __shared__ float2 stg[NB];
+    const unsigned n = meta_ch[0];
+    const unsigned G = gridDim.x,
+                   off = xmap ? (blockIdx.x & 7u) * (G >> 3) + (blockIdx.x >> 3) : blockIdx.x;
+    for (unsigned c = off; c < n; c += G) {
+        const TChunk t = chunks[c];
+        for (uint32_t i0 = t.b; i0 < t.e; i0 += NB) {
+            float2 r[U];
+            unsigned s[U], d[U];
+            // (clamped-index loads, all in flight together)
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const uint32_t ic = min(i0 + u * kTThreads + threadIdx.x, t.e - 1u);
+                r[u] = in[ic];
+                s[u] = slot[ic];
+                d[u] = dstp[ic];
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const unsigned j = u * kTThreads + threadIdx.x;
+                if (i0 + j < t.e) stg[(j & ~(kTFinalNB - 1u)) | (s[u] & (kTFinalNB - 1u))] = r[u];
+            }
+            __syncthreads();
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const unsigned j = u * kTThreads + threadIdx.x;
+                if (i0 + j < t.e && d[u] < ntot) vals[(size_t)d[u] * stride] = stg[j];
             }
             __syncthreads();
         }
@@ -3301,11 +3507,22 @@ struct Part {
     uint16_t *t_lkey = nullptr;
     double *t_fsc = nullptr;  // frequency / c per channel
     void *t_a = nullptr;  // records in bin order (the value pass's output)
+    // the permutation a kept layout's hits replay (bucket_tiled; null on a
+    // call that cannot end in keep_layout): each visibility's position in
+    // t_a, each t_a record's staging slot in its batch of the final move, and
+    // the final position of every staged record
+    unsigned *t_pos = nullptr, *t_dst = nullptr;
+    uint16_t *t_slot = nullptr;
+    unsigned t_ntot = 0;  // padded records of the final arrays
 };
 
 struct Plan {
     Geo g;
     VisRec *recs = nullptr;
+    // fp32 two-level inverts (pad4 && g.tiled): `recs` holds the records'
+    // values (float2[ntot]) and `offs` their packed offsets (RecC's lo, hi),
+    // two arrays in the one "recs" scratch
+    uint2 *offs = nullptr;
     Part pt;
     bool f64 = false;                // fp64 NUFFT (epsilon < 1e-7): VisRec64, c128 planes
     bool subsort = false;            // 16x16-cell buckets re-ordered by cell (k_subsort)
@@ -3376,7 +3593,9 @@ static size_t grid_budget_bytes(size_t need_other) {
     const size_t held_other = ws.held(ws_name("recs")) + ws.held(ws_name("key_rank")) +
                               ws.held(ws_name("degrid_acc")) + ws.held(ws_name("recs_pad")) +
                               ws.held(ws_name("rec_cls")) + ws.held(ws_name("recs_a")) +
-                              ws.held(ws_name("rec_lkey")) + ws.held(ws_name("t_m2"));
+                              ws.held(ws_name("rec_lkey")) + ws.held(ws_name("t_m2")) +
+                              ws.held(ws_name("t_pos")) + ws.held(ws_name("t_slot")) +
+                              ws.held(ws_name("t_dst"));
     const size_t avail = free_b + held_planes + held_other;
     const size_t reserve = std::max<size_t>((size_t)6 << 30, total_b / 16);
     const size_t need = need_other + reserve;
@@ -3999,7 +4218,12 @@ static Plan plan_geometry_once(const Inputs &in, bool grid_mode, hipStream_t st,
     // two-level plans: the bin-ordered records + their cell keys, then the
     // final (for the invert 4-padded, ~1.05x) copy
     const double tiled_rec = P.f64 ? sizeof(VisRec64) : grid_mode ? sizeof(RecC) : sizeof(VisRec);
-    const double rec_bytes = g.tiled     ? 2.1 * tiled_rec + sizeof(uint16_t) - sizeof(unsigned)
+    // (a two-level fp32 invert may keep its layout: 10 B per visibility of
+    // recorded permutation -- t_pos, t_slot, t_dst)
+    const double kept_perm =
+        g.tiled && grid_mode && !P.f64 ? 2 * sizeof(unsigned) + sizeof(uint16_t) : 0;
+    const double rec_bytes = g.tiled     ? 2.1 * tiled_rec + sizeof(uint16_t) - sizeof(unsigned) +
+                                               kept_perm
                              : P.f64     ? sizeof(VisRec64)
                              : P.subpad  ? sizeof(RecC) + 1 + 1.35 * sizeof(RecC)
                                          : sizeof(VisRec);
@@ -4009,7 +4233,8 @@ static Plan plan_geometry_once(const Inputs &in, bool grid_mode, hipStream_t st,
         Workspace::get().drop(ws_name("recs_pad"));
         Workspace::get().drop(ws_name("rec_cls"));
     }
-    for (const char *n : {"recs_a", "rec_lkey", "t_m1", "t_m2", "t_tot", "t_cbase", "t_stot"})
+    for (const char *n : {"recs_a", "rec_lkey", "t_m1", "t_m2", "t_tot", "t_cbase", "t_stot", "t_pos",
+                          "t_slot", "t_dst"})
         if (!g.tiled) Workspace::get().drop(ws_name(n));
     for (const char *n : {"key_rank", "hist", "offs", "gsum", "gofs"})
         if (g.tiled) Workspace::get().drop(ws_name(n));
@@ -4375,7 +4600,11 @@ static void launch_grid_mfma_pad(const Plan &P, int p_lo, int p_hi, hipStream_t 
         k_grid_mfma_pad<W, WS, 4><<<nu, 64, grid_mfma_pad_lds<4>(), st>>>(
             P.g, P.recs_pad, P.pt.fitems + 16 * (size_t)r.first, nu, (float *)P.grid, p_lo, p_hi,
             P.core);
-    } else
+    } else if (P.offs)  // (two-level plans: values and offsets apart)
+        k_grid_mfma_pad_soa<W, WS><<<n, 64, grid_mfma_pad_lds<1>(), st>>>(
+            P.g, reinterpret_cast<const float2 *>(P.recs), P.offs, P.pt.fitems + r.first, n,
+            (float *)P.grid, p_lo, p_hi, P.core);
+    else
         k_grid_mfma_pad<W, WS, 1><<<n, 64, grid_mfma_pad_lds<1>(), st>>>(
             P.g, reinterpret_cast<const RecC *>(P.recs), P.pt.fitems + r.first, n, (float *)P.grid,
             p_lo, p_hi, P.core);
@@ -4900,9 +5129,20 @@ static int cu_count() {
 // (SDP_HIP_REUSE_BUCKETS): the kept plan's bins, chunks and cell bases are
 // valid, so only the value pass, the recount of the chunks' cells and the
 // final move run.
+//
+// The layout cache (KeptLayout), fp32 inverts only.  `record`: the value
+// pass and the final move also write the permutation they apply (t_pos,
+// t_slot, t_dst: 10 B per visibility) -- a kept layout's first hit, which
+// runs values_only with the recount and leaves values, offsets and the
+// permutation consistent (a miss does not pay for hits that may never come;
+// SDP_HIP_LAYOUT_RECORD=1 records in the keeping call instead).
+// `replay`: a later hit on the kept plan P -- k_t_values and k_t_replay move the
+// new values along that permutation; everything else of the layout (the
+// offsets and pads in the final arrays included) stays as the keeping call
+// left it.
 static void bucket_tiled(Plan &P, const Inputs &in, bool grid_mode, hipStream_t st,
                          bool values_only, const std::function<void()> &after_clear,
-                         double *slots) {
+                         double *slots, bool record = false, bool replay = false) {
     const Geo &g = P.g;
     Part &pt = P.pt;
     const int nb = g.nbins;
@@ -4942,12 +5182,20 @@ static void bucket_tiled(Plan &P, const Inputs &in, bool grid_mode, hipStream_t 
         pt.t_lkey = scratch<uint16_t>("rec_lkey", std::max<int64_t>(nvis, 1));
         pt.t_fsc = scratch<double>("t_fscale", g.nchan);
         pt.t_a = scratch<char>("recs_a", (size_t)std::max<int64_t>(nvis, 1) * rsz);
+        pt.t_pos = pt.t_dst = nullptr;
+        pt.t_slot = nullptr;
         pt.nbad = scratch<unsigned long long>("nbad", 2);  // {out of grid, dropped}
         pt.meta = scratch<unsigned>("meta", g.nps + 7);
         SDP_HIP_CHECK(hipMemsetAsync(pt.t_binc, 0, nb * sizeof(unsigned), st));
         SDP_HIP_CHECK(hipMemsetAsync(pt.t_binsum, 0, nb * sizeof(unsigned long long), st));
         SDP_HIP_CHECK(hipMemsetAsync(pt.nbad, 0, 2 * sizeof(unsigned long long), st));
         if (after_clear) after_clear();
+    }
+    record = record && kind == 0 && !replay;
+    if (record) {
+        pt.t_pos = scratch<unsigned>("t_pos", std::max<int64_t>(nvis, 1));
+        pt.t_slot = scratch<uint16_t>("t_slot", std::max<int64_t>(nvis, 1));
+        pt.t_dst = scratch<unsigned>("t_dst", std::max<int64_t>(nvis, 1));
     }
     k_fscale<<<grid1d(g.nchan, 256), 256, 0, st>>>(in.freq, g.nchan, pt.t_fsc);
     const TypedIn ti = typed_inputs(g, in, st);
@@ -4966,7 +5214,8 @@ static void bucket_tiled(Plan &P, const Inputs &in, bool grid_mode, hipStream_t 
                     <<<pt.t_g1, kT1Threads, lds_bins, st>>>(
                         g, nvis, pt.t_vpw, in.uvw, in.uvw_rs, pt.t_fsc,
                         G ? static_cast<const VT *>(in.vis) : nullptr, in.vrs, in.vcs, wgt, wrs,
-                        wcs, x, sl, pt.t_binbase, pt.t_m1, pt.t_a, pt.t_lkey);
+                        wcs, x, sl, pt.t_binbase, pt.t_m1, pt.t_a, pt.t_lkey,
+                        record ? pt.t_pos : nullptr);
             });
         };
         auto grid_kind = [&](auto vt_tag) {
@@ -4995,18 +5244,50 @@ static void bucket_tiled(Plan &P, const Inputs &in, bool grid_mode, hipStream_t 
         const int xmap = (gch % 8 == 0 && env_int("SDP_HIP_TFINAL_XCD", 1) != 0) ? 1 : 0;
         k_t_final_s<K, NB><<<gch, kTThreads, lds, st>>>(pt.t_chunks, pt.t_meta_ch, pt.t_lkey,
                                                          pt.t_m2, pt.t_stot, pt.t_cbase, pt.t_a,
-                                                         P.recs, xmap);
+                                                         P.recs, xmap, P.offs,
+                                                         record ? pt.t_slot : nullptr,
+                                                         record ? pt.t_dst : nullptr);
     };
     auto final_move = [&] {
         // batches of 4096 (RecC), 2048 (VisRec, Rec64) records staged in LDS
         if (kind == 3) staged(std::integral_constant<int, 3>{}, std::integral_constant<int, 2048>{});
-        else if (kind == 0) staged(std::integral_constant<int, 0>{}, std::integral_constant<int, 4096>{});
+        else if (kind == 0) staged(std::integral_constant<int, 0>{}, std::integral_constant<int, kTFinalNB>{});
         else staged(std::integral_constant<int, 1>{}, std::integral_constant<int, 2048>{});
         SDP_HIP_CHECK(hipGetLastError());
     };
     const unsigned gseg =
         (unsigned)std::min<int64_t>((int64_t)pt.t_maxseg * (kBinCells / 256), 8192);
     const unsigned gcol = (unsigned)std::min<int64_t>((int64_t)nb * (kBinCells / 256), 8192);
+    if (replay) {
+        SDP_REQUIRE(values_only && kind == 0 && pt.t_pos && pt.t_slot && pt.t_dst,
+                    "layout replay: the kept plan holds no recorded permutation");
+        const int stride = P.offs ? 1 : 2;  // (interleaved RecC: the value half in place)
+        if (nvis <= 0) return;
+        auto go = [&](auto vt_tag) {
+            using VT = typename decltype(vt_tag)::type;
+            ti.dispatch([&](auto wt_tag, auto fb_tag) {
+                k_t_values<VT, decltype(wt_tag)::value, decltype(fb_tag)::value>
+                    <<<pt.t_g1, kT1Threads, 0, st>>>(
+                        g, nvis, pt.t_vpw, in.uvw, in.uvw_rs, pt.t_fsc,
+                        static_cast<const VT *>(in.vis), in.vrs, in.vcs, wgt, wrs, wcs, x, slots,
+                        pt.t_pos, (unsigned)pt.nrec, static_cast<float2 *>(pt.t_a));
+            });
+        };
+        if (in.vis_dtype == SDP_HIP_C128) go(TypeTag<double2>{});
+        else go(TypeTag<float2>{});
+        const int xmap = (gch % 8 == 0 && env_int("SDP_HIP_TFINAL_XCD", 1) != 0) ? 1 : 0;
+        float2 *vals = reinterpret_cast<float2 *>(P.recs);
+        if (env_int("SDP_HIP_TREPLAY_NB", kTFinalNB) == 2 * kTFinalNB)
+            k_t_replay<2 * kTFinalNB><<<gch, kTThreads, 0, st>>>(
+                pt.t_chunks, pt.t_meta_ch, pt.t_slot, pt.t_dst, static_cast<const float2 *>(pt.t_a),
+                vals, pt.t_ntot, xmap, stride);
+        else
+            k_t_replay<kTFinalNB><<<gch, kTThreads, 0, st>>>(
+                pt.t_chunks, pt.t_meta_ch, pt.t_slot, pt.t_dst, static_cast<const float2 *>(pt.t_a),
+                vals, pt.t_ntot, xmap, stride);
+        SDP_HIP_CHECK(hipGetLastError());
+        return;
+    }
     if (values_only) {
         // The value pass ranks a record inside its workgroup's slice of a
         // bin by LDS cursors its 8 waves race on, so where a slice straddles
@@ -5064,17 +5345,24 @@ static void bucket_tiled(Plan &P, const Inputs &in, bool grid_mode, hipStream_t 
     const size_t ntot = (size_t)m[5 + nps];
     pt.dropped = m[6 + nps] != 0;
     P.recs = reinterpret_cast<VisRec *>(scratch<char>("recs", (ntot + 1) * rsz));
+    // RecC records: the values in the first half of the scratch, the offsets
+    // behind them (ntot is a multiple of 4: every cell is padded to one)
+    const bool split = kind == 0 && env_int("SDP_HIP_RECS_SPLIT", 1) != 0;
+    P.offs = split ? reinterpret_cast<uint2 *>(reinterpret_cast<char *>(P.recs) +
+                                               ntot * sizeof(float2))
+                   : nullptr;
+    pt.t_ntot = (unsigned)ntot;
     pt.fitems = scratch<FineItem>("fitems", (size_t)pt.nitems + 1);
     const unsigned gfin = (unsigned)std::min(nb, 4096);
     if (P.pad4)
         k_t_cellfin<true, 0><<<gfin, 256, 0, st>>>(g, pt.t_nbl, pt.t_tot, pt.t_bofs, P.chunk,
-                                                   pt.t_cbase, P.recs, pt.fitems);
+                                                   pt.t_cbase, P.recs, P.offs, pt.fitems);
     else if (P.pad64)
         k_t_cellfin<true, 3><<<gfin, 256, 0, st>>>(g, pt.t_nbl, pt.t_tot, pt.t_bofs, P.chunk,
-                                                   pt.t_cbase, P.recs, pt.fitems);
+                                                   pt.t_cbase, P.recs, nullptr, pt.fitems);
     else
         k_t_cellfin<false, 1><<<gfin, 256, 0, st>>>(g, pt.t_nbl, pt.t_tot, pt.t_bofs, P.chunk,
-                                                    pt.t_cbase, nullptr, pt.fitems);
+                                                    pt.t_cbase, nullptr, nullptr, pt.fitems);
     if (nvis > 0) final_move();
     SDP_HIP_CHECK(hipGetLastError());
 }
@@ -5084,11 +5372,12 @@ static void bucket_tiled(Plan &P, const Inputs &in, bool grid_mode, hipStream_t 
 // `after_clear` runs once the histogram clearing is queued (work put on
 // another stream there does not compete with that memset).
 static void bucket_all(Plan &P, const Inputs &in, bool grid_mode, hipStream_t st,
-                       const std::function<void()> &after_clear = nullptr) {
+                       const std::function<void()> &after_clear = nullptr,
+                       bool record = false) {
     double *slots = in.x.sumwt ? scratch<double>("sumwt_slots", kSumSlots) : nullptr;
     if (slots) SDP_HIP_CHECK(hipMemsetAsync(slots, 0, kSumSlots * sizeof(double), st));
     if (P.g.tiled) {  // (reads its metadata itself)
-        bucket_tiled(P, in, grid_mode, st, false, after_clear, slots);
+        bucket_tiled(P, in, grid_mode, st, false, after_clear, slots, record);
         return;
     }
     bucket_part(P, in, grid_mode, st, false, after_clear);
@@ -5369,11 +5658,17 @@ static void ms2dirty(const Inputs &in, double *dirty, int64_t sx, int64_t sy,
         // value pass only (weight sums included)
         double *slots = in.x.sumwt ? scratch<double>("sumwt_slots", kSumSlots) : nullptr;
         if (slots) SDP_HIP_CHECK(hipMemsetAsync(slots, 0, kSumSlots * sizeof(double), st));
-        if (P.g.tiled) bucket_tiled(P, inx, true, st, true, nullptr, slots);
+        // (a kept layout's first hit runs the value pass, the recount and
+        // the final move, as SDP_HIP_REUSE_BUCKETS on a two-level plan does,
+        // and records the permutation they apply; later hits replay it)
+        const bool replay = hit && P.pt.t_pos != nullptr;
+        if (P.g.tiled) bucket_tiled(P, inx, true, st, true, nullptr, slots, hit && !replay, replay);
         else bucket_part(P, inx, true, st, true);
         if (slots) sum_slots(slots, in.x.sumwt, st);
+        if (hit && !replay && P.pt.t_pos) keep_layout(lkey, P);  // (... with the permutation)
     } else {
-        bucket_all(P, inx, true, st, start_zero);
+        bucket_all(P, inx, true, st, start_zero,
+                   cacheable && env_int("SDP_HIP_LAYOUT_RECORD", 0) == 1);
     }
     if (P.subsort) subsort_items(P, st);
     if (keep) keep_buckets(P, in);
