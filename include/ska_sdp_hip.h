@@ -693,6 +693,43 @@ int sdp_hip_clean_plane(int algorithm, int nscales, int ny, int nx,
                         char *errbuf, size_t errbuf_len);
 
 /*
+ * Complex Hogbom CLEAN minor cycles of a Stokes Q and a Stokes U plane as
+ * P = Q + iU (Pratley & Johnston-Hollitt 2016), replacing the numpy loop of
+ * the reference's hogbom_complex (src/ska_sdp_func_python/image/
+ * cleaners.py:136-232).  Everything is fp64, contiguous and updated in place.
+ *   res      [2, ny, nx]: plane 0 is Q, plane 1 is U
+ *   psf      [psf_ny, psf_nx], shared by both planes (>= 2 x 2); pixel
+ *            (psf_ny/2, psf_nx/2) lands on the peak, the patch is
+ *            [peak - n/2, peak + n/2) clipped to the image
+ *   window   [ny, nx] or NULL: multiplies both planes in the search
+ *   comps    [2, ny, nx], accumulated into
+ *   pmax     the PSF's maximum, > 0 (it need not be 1)
+ * One cycle, every step a single IEEE operation without contraction:
+ *   search   the key of a pixel is hypot(q * w, u * w) (w = 1 without a
+ *            window); the largest key wins, the lower flat index on a tie at
+ *            every reduction level; a NaN key is never selected and an
+ *            all-NaN plane gives index 0
+ *   value    mval_q = (q * gain) * rinv and mval_u = (u * gain) * rinv with
+ *            rinv = 1.0 / pmax formed once per call: numpy's division of a
+ *            complex scalar by a real one (NOT (q * gain) / pmax)
+ *   comps    comps_q[peak] += mval_q, comps_u[peak] += mval_u
+ *   residual on the patch q -= psf * mval_q and u -= psf * mval_u, one
+ *            multiplication and one subtraction each
+ *   stop     after the subtraction, once hypot(q, u) at the peak pixel is
+ *            < absthresh -- absthresh itself, not the 0.9 * absthresh of
+ *            sdp_hip_clean_plane; that cycle counts
+ * *niter_done is the reference's iteration count, *stop_reason
+ * SDP_HIP_CLEAN_STOP_NITER or _THRESHOLD.  The call returns after the last
+ * cycle has run.
+ */
+int sdp_hip_clean_plane_complex(int ny, int nx, int psf_ny, int psf_nx,
+                                double *res, const double *psf,
+                                const double *window, double *comps,
+                                double gain, double pmax, double absthresh,
+                                int niter, int *niter_done, int *stop_reason,
+                                void *stream, char *errbuf, size_t errbuf_len);
+
+/*
  * Multi-scale multi-frequency CLEAN minor cycles on one polarisation (Rau &
  * Cornwell 2011, Algorithm 1), replacing the numpy loop of the reference's
  * msmfsclean (src/ska_sdp_func_python/image/cleaners.py:831-876, with

@@ -29,6 +29,10 @@
 // every reduction level breaks ties on the lower flat index, and scales are
 // compared with the reference's strict '>' (the lower scale wins a tie).
 // NaN search values are never selected.
+//
+// sdp_hip_clean_plane_complex is the same scheme for the reference's
+//   hogbom_complex       cleaners.py:136-232
+// on a Q and a U plane cleaned as P = Q + iU (k_select_c / k_update_c below).
 #include "sdp_common.h"
 
 #include <climits>
@@ -257,6 +261,121 @@ __global__ __launch_bounds__(kSelThreads) void k_select(Params p, State *st,
     st->active = 1;
 }
 
+// ---- complex Hogbom: Q and U cleaned together as P = Q + iU ------------------
+// (hogbom_complex, cleaners.py:136-232).  The same two kernels per cycle on a
+// residual of two planes: the search key of a pixel is hypot(q * w, u * w), one
+// thread owns the pixel in both planes and reads its PSF value once.  Params
+// carries the geometry and the gain (ns 1, msclean 0); 1 / pmax and the
+// threshold, which is not scaled by 0.9 here, are kernel arguments.
+struct StateC {
+    int done, active, iter, reason;  // as State
+    int peak_y, peak_x;
+    double mval_q, mval_u;
+};
+
+__device__ __forceinline__ double key_c(double q, double u, size_t pix,
+                                        const double *__restrict__ win) {
+    return win ? hypot(q * win[pix], u * win[pix]) : hypot(q, u);
+}
+
+// init: every tile of the image, no subtraction.
+__global__ __launch_bounds__(kThreads) void k_update_c(Params p, double absthresh, int init,
+                                                       StateC *st, double *res,
+                                                       const double *__restrict__ psf,
+                                                       const double *__restrict__ win,
+                                                       double *tkey, int *tidx) {
+    int ty = blockIdx.y, tx = blockIdx.x;
+    int py = 0, px = 0;
+    double mq = 0.0, mu = 0.0;
+    Box b{0, 0, 0, 0};
+    if (!init) {
+        if (!st->active) return;
+        py = st->peak_y;
+        px = st->peak_x;
+        mq = st->mval_q;
+        mu = st->mval_u;
+        b = patch_box(p, py, px);
+        ty += b.y0 / kTileY;
+        tx += b.x0 / kTileX;
+        if (ty > (b.y1 - 1) / kTileY || tx > (b.x1 - 1) / kTileX) return;
+    }
+    const int hy = p.pny / 2, hx = p.pnx / 2;
+    const size_t plane = (size_t)p.ny * p.nx;
+    const int x = tx * kTileX + (threadIdx.x & 63);
+    Best best{-1.0, INT_MAX};
+#pragma unroll
+    for (int k = 0; k < kTileY / 4; ++k) {
+        const int y = ty * kTileY + (threadIdx.x >> 6) + 4 * k;
+        if (y >= p.ny || x >= p.nx) continue;
+        const size_t pix = (size_t)y * p.nx + x;
+        double q = res[pix], u = res[plane + pix];
+        if (y >= b.y0 && y < b.y1 && x >= b.x0 && x < b.x1) {
+            const double t = psf[(size_t)(hy + y - py) * p.pnx + (hx + x - px)];
+            q = q - t * mq;
+            u = u - t * mu;
+            res[pix] = q;
+            res[plane + pix] = u;
+            // the stop test, after the subtraction and on absthresh itself (cleaners.py:222)
+            if (y == py && x == px && hypot(q, u) < absthresh) {
+                st->done = 1;
+                st->reason = SDP_HIP_CLEAN_STOP_THRESHOLD;
+            }
+        }
+        const double key = key_c(q, u, pix, win);
+        if (better(key, (int)pix, best.key, best.idx)) best = {key, (int)pix};
+    }
+    __shared__ Best s_best[kThreads / 64];
+    best = wave_best(best);
+    if ((threadIdx.x & 63) == 0) s_best[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kThreads / 64; ++w)
+            if (better(s_best[w].key, s_best[w].idx, best.key, best.idx)) best = s_best[w];
+        const size_t t = (size_t)ty * p.ntx + tx;
+        tkey[t] = best.key;
+        tidx[t] = best.idx;
+    }
+}
+
+__global__ __launch_bounds__(kSelThreads) void k_select_c(Params p, double rinv, StateC *st,
+                                                          const double *__restrict__ res,
+                                                          double *comps,
+                                                          const double *__restrict__ tkey,
+                                                          const int *__restrict__ tidx) {
+    __shared__ Best s_wave[kSelThreads / 64];
+    __shared__ int s_done;
+    if (threadIdx.x == 0) s_done = st->done;
+    __syncthreads();
+    if (s_done) {
+        if (threadIdx.x == 0) st->active = 0;
+        return;
+    }
+    const int ntiles = p.ntx * p.nty;
+    Best best{-1.0, INT_MAX};
+    for (int t = threadIdx.x; t < ntiles; t += kSelThreads)
+        if (better(tkey[t], tidx[t], best.key, best.idx)) best = {tkey[t], tidx[t]};
+    best = wave_best(best);
+    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int w = 1; w < kSelThreads / 64; ++w)
+        if (better(s_wave[w].key, s_wave[w].idx, best.key, best.idx)) best = s_wave[w];
+    // numpy.argmax of an all-NaN plane is 0 as well
+    const int pix = best.idx == INT_MAX ? 0 : best.idx;
+    const size_t plane = (size_t)p.ny * p.nx;
+    // numpy's complex / real: one reciprocal, then a product per component
+    const double mq = (res[pix] * p.gain) * rinv;
+    const double mu = (res[plane + pix] * p.gain) * rinv;
+    comps[pix] = comps[pix] + mq;
+    comps[plane + pix] = comps[plane + pix] + mu;
+    st->iter += 1;
+    st->peak_y = pix / p.nx;
+    st->peak_x = pix - (pix / p.nx) * p.nx;
+    st->mval_q = mq;
+    st->mval_u = mu;
+    st->active = 1;
+}
+
 }  // namespace clean
 }  // namespace sdp
 
@@ -326,6 +445,65 @@ int sdp_hip_clean_plane(int algorithm, int nscales, int ny, int nx, int psf_ny, 
             SDP_HIP_CHECK(hipGetLastError());
             issued += n;
             SDP_HIP_CHECK(hipMemcpyAsync(&host, state, sizeof(State), hipMemcpyDeviceToHost, st));
+            SDP_HIP_CHECK(hipStreamSynchronize(st));
+        }
+        *niter_done = host.iter;
+        *stop_reason = host.done ? host.reason : SDP_HIP_CLEAN_STOP_NITER;
+    });
+}
+
+int sdp_hip_clean_plane_complex(int ny, int nx, int psf_ny, int psf_nx, double *res,
+                                const double *psf, const double *window, double *comps,
+                                double gain, double pmax, double absthresh, int niter,
+                                int *niter_done, int *stop_reason, void *stream, char *errbuf,
+                                size_t errbuf_len) {
+    using namespace sdp;
+    using namespace sdp::clean;
+    return guarded(errbuf, errbuf_len, [&] {
+        SDP_REQUIRE(ny > 0 && nx > 0 && (int64_t)ny * nx < INT_MAX,
+                    "image must be non-empty with fewer than 2^31 pixels");
+        SDP_REQUIRE(psf_ny >= 2 && psf_nx >= 2, "psf must be at least 2 x 2");
+        SDP_REQUIRE(niter > 0, "niter must be positive");
+        SDP_REQUIRE(pmax > 0.0, "pmax must be positive");
+        SDP_REQUIRE(res && psf && comps && niter_done && stop_reason, "null pointer argument");
+        Params p{};
+        p.ns = 1;
+        p.ny = ny;
+        p.nx = nx;
+        p.pny = psf_ny;
+        p.pnx = psf_nx;
+        p.ntx = (nx + kTileX - 1) / kTileX;
+        p.nty = (ny + kTileY - 1) / kTileY;
+        p.gain = gain;
+        p.pmax = pmax;
+        const double rinv = 1.0 / pmax;
+
+        const hipStream_t st = as_stream(stream);
+        const size_t ntiles = (size_t)p.ntx * p.nty;
+        StateC *state = scratch<StateC>("clean_complex_state", 1);
+        double *tkey = scratch<double>("clean_complex_tile_key", ntiles);
+        int *tidx = scratch<int>("clean_complex_tile_idx", ntiles);
+        SDP_HIP_CHECK(hipMemsetAsync(state, 0, sizeof(StateC), st));
+        k_update_c<<<dim3(p.ntx, p.nty), kThreads, 0, st>>>(p, absthresh, 1, state, res, psf,
+                                                            window, tkey, tidx);
+        SDP_HIP_CHECK(hipGetLastError());
+
+        // tiles a patch of 2 * (n // 2) pixels can touch at any offset
+        auto span = [](int half, int tile, int total) {
+            return std::min(total, (2 * half + tile - 2) / tile + 1);
+        };
+        const dim3 ugrid(span(psf_nx / 2, kTileX, p.ntx), span(psf_ny / 2, kTileY, p.nty));
+        StateC host{};
+        for (int issued = 0; issued < niter && !host.done;) {
+            const int n = std::min(kBatch, niter - issued);
+            for (int i = 0; i < n; ++i) {
+                k_select_c<<<1, kSelThreads, 0, st>>>(p, rinv, state, res, comps, tkey, tidx);
+                k_update_c<<<ugrid, kThreads, 0, st>>>(p, absthresh, 0, state, res, psf, window,
+                                                       tkey, tidx);
+            }
+            SDP_HIP_CHECK(hipGetLastError());
+            issued += n;
+            SDP_HIP_CHECK(hipMemcpyAsync(&host, state, sizeof(StateC), hipMemcpyDeviceToHost, st));
             SDP_HIP_CHECK(hipStreamSynchronize(st));
         }
         *niter_done = host.iter;

@@ -225,6 +225,11 @@ SIGNATURES = {
         c_vp, c_vp, c_int, c_vp,                    # coupling_diag (host), scale_kernels, extent, comps
         c_dbl, c_dbl, c_dbl, c_int,                 # gain, pmax, absthresh, niter
         ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_vp] + _ERR,
+    "sdp_hip_clean_plane_complex": [
+        c_int, c_int, c_int, c_int,                 # ny, nx, psf_ny, psf_nx
+        c_vp, c_vp, c_vp, c_vp,                     # res [2, ny, nx], psf, window, comps [2, ny, nx]
+        c_dbl, c_dbl, c_dbl, c_int,                 # gain, pmax, absthresh, niter
+        ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_vp] + _ERR,
     "sdp_hip_mfsclean_plane": [
         c_int, c_int, c_int, c_int, c_int, c_int,   # nscales, nmoment, ny, nx, psf_ny, psf_nx
         c_vp, c_vp, c_vp, c_vp, c_int,              # smresidual, m_model, ssmmpsf, scale_kernels, extent

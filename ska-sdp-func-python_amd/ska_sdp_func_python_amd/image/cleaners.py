@@ -1,10 +1,12 @@
 """Image-plane cleaners on 2-D arrays and moment stacks (reference
-src/ska_sdp_func_python/image/cleaners.py): ``hogbom`` (:23-133), ``msclean``
+src/ska_sdp_func_python/image/cleaners.py): ``hogbom`` (:23-133),
+``hogbom_complex`` (:136-232, Q + iU cleaned as one complex image), ``msclean``
 (:279-470) with the scale-stack helpers (:473-562), and ``msmfsclean``
 (:686-898) with its set-up helpers (:1034-1104).
 
-The minor cycles run on the device in ``kernels.clean_plane``
-(csrc/clean.hip) and ``kernels.mfsclean_plane`` (csrc/mfsclean.hip): the
+The minor cycles run on the device in ``kernels.clean_plane`` and
+``kernels.clean_plane_complex`` (csrc/clean.hip) and
+``kernels.mfsclean_plane`` (csrc/mfsclean.hip): the
 full-image search and the shifted PSF subtraction of every cycle, in fp64 and
 in the reference's arithmetic order.  numpy input gives numpy output, device
 tensors give device tensors.
@@ -23,7 +25,8 @@ import torch
 
 from .. import _device, kernels
 
-__all__ = ["hogbom", "msclean", "msmfsclean", "hogbom_run", "msclean_run", "msmfsclean_run",
+__all__ = ["hogbom", "hogbom_complex", "msclean", "msmfsclean", "hogbom_run", "hogbom_complex_run",
+           "msclean_run", "msmfsclean_run",
            "create_scalestack", "convolve_scalestack", "convolve_convolve_scalestack",
            "calculate_scale_moment_residual", "calculate_scale_scale_moment_moment_psf",
            "calculate_scale_inverse_moment_moment_hessian", "spheroidal_function"]
@@ -69,6 +72,58 @@ def hogbom(dirty, psf, window, gain, thresh, niter, fracthresh, prefix=""):
     :return: component image, residual image
     """
     return hogbom_run(dirty, psf, window, gain, thresh, niter, fracthresh, prefix)[:2]
+
+
+def hogbom_complex_run(dirty_q, dirty_u, psf_q, psf_u, window, gain, thresh, niter, fracthresh):
+    """``hogbom_complex`` that also reports what the minor cycle did: returns
+    (comps_q, comps_u, res_q, res_u, {"niter": cycles run, "stop": "niter" | "threshold"})."""
+    assert 0.0 < gain < 2.0
+    assert niter > 0
+    dpsf, dpsf_u = _dev64(psf_q), _dev64(psf_u)
+    assert dpsf.shape == dpsf_u.shape and bool((dpsf == dpsf_u).all())
+    pmax = float(dpsf.max())
+    assert pmax > 0.0
+    res = torch.stack([_dev64(dirty_q), _dev64(dirty_u)])
+    absolutethresh = max(thresh, fracthresh * float(torch.hypot(res[0], res[1]).max()))
+    comps = torch.zeros_like(res)
+    win = None if window is None else _dev64(window)
+    log.info("hogbom_complex: This minor cycle will stop at %d iterations or peak < %s", niter,
+             absolutethresh)
+    done, stop = kernels.clean_plane_complex(res, dpsf, comps, gain, pmax, absolutethresh, niter,
+                                             window=win)
+    log.info("hogbom_complex: End of minor cycle: %d iterations (%s)", done, stop)
+    return (_device.like_input(comps[0], dirty_q), _device.like_input(comps[1], dirty_q),
+            _device.like_input(res[0], dirty_q), _device.like_input(res[1], dirty_q),
+            {"niter": done, "stop": stop})
+
+
+def hogbom_complex(dirty_q, dirty_u, psf_q, psf_u, window, gain, thresh, niter, fracthresh):
+    """Complex Hogbom CLEAN of polarised data (Pratley & Johnston-Hollitt
+    2016): Stokes Q and U are cleaned together as P = Q + iU, the peak is
+    searched on |P|, so that the result does not depend on the polarisation
+    angle.
+
+    :param dirty_q: dirty Q image [ny, nx]
+    :param dirty_u: dirty U image [ny, nx]
+    :param psf_q: point spread function of Q, any size; its maximum must be
+                  positive but need not be 1 (the components are divided by it)
+    :param psf_u: point spread function of U, which must equal ``psf_q``
+    :param window: array multiplying Q and U in the search, or None
+    :param gain: loop gain
+    :param thresh: stop once |P| at the peak, after the subtraction, is below
+                   max(thresh, fracthresh * max|P|) -- without the factor 0.9
+                   of ``hogbom``
+    :param niter: maximum number of components
+    :param fracthresh: fractional threshold
+    :return: Q components, U components, Q residual, U residual
+
+    Arithmetic (csrc/clean.hip, ``kernels.clean_plane_complex``): the search
+    key is hypot(q * w, u * w), the first maximum in row-major order wins, and
+    the component is (P[peak] * gain) * (1 / pmax) -- numpy's division of a
+    complex scalar by a real one.
+    """
+    return hogbom_complex_run(dirty_q, dirty_u, psf_q, psf_u, window, gain, thresh, niter,
+                              fracthresh)[:4]
 
 
 def msclean_run(dirty, psf, window, sensitivity, gain, thresh, niter, scales, fracthresh,

@@ -12,7 +12,13 @@ csrc/clean.hip and csrc/mfsclean.hip); the restore is a circular convolution
 with ``torch.fft`` on the device.  Pixels may be numpy arrays or device
 tensors; outputs follow the dirty (model) image.
 
-``hogbom-complex`` is not provided and raises ``ValueError``.
+The complex Hogbom clean of Q + iU (``cleaners.hogbom_complex``) and its list
+driver ``complex_hogbom_kernel_list`` (:394-511) are provided and are called
+directly.  The string dispatch ``algorithm="hogbom-complex"`` of
+``deconvolve_list`` / ``deconvolve_cube`` is still refused with ``ValueError``
+(tests/test_clean_cpu.py pins that): a caller who wants ``psf_support`` or a
+window applies ``bound_psf_list`` / ``find_window_list`` first, as
+``deconvolve_list`` does for the other cleaners.
 """
 
 import logging
@@ -22,15 +28,15 @@ import numpy
 import torch
 
 from .. import _device
-from ..datamodels import Image
-from .cleaners import hogbom, msclean, msmfsclean
+from ..datamodels import Image, PolarisationFrame
+from .cleaners import hogbom, hogbom_complex, msclean, msmfsclean
 from .gather_scatter import image_gather_channels, image_scatter_channels
 from .operations import convert_clean_beam_to_degrees, convert_clean_beam_to_pixels
 from .taylor_terms import (calculate_image_list_frequency_moments,
                            calculate_image_list_from_frequency_taylor_terms)
 
 __all__ = ["deconvolve_cube", "deconvolve_list", "hogbom_kernel_list", "msclean_kernel_list",
-           "mmclean_kernel_list", "find_window_list", "bound_psf_list", "check_psf_peak", "common_arguments",
+           "mmclean_kernel_list", "complex_hogbom_kernel_list", "find_window_list", "bound_psf_list", "check_psf_peak", "common_arguments",
            "restore_cube", "restore_list", "fit_psf"]
 
 log = logging.getLogger("func-python-logger")
@@ -244,6 +250,64 @@ def msclean_kernel_list(dirty_list, prefix, psf_list, window_list, sensitivity_l
         lambda d, p, channel, pol: msclean(d, p, _plane(window_list, channel, pol),
                                            _plane(sensitivity_list, channel, pol), gain, thresh,
                                            niter, scales, fracthresh, prefix))
+
+
+def complex_hogbom_kernel_list(dirty_list, psf_list, window_list, **kwargs):
+    """Complex Hogbom clean of single-channel stokesIQUV images: I and V
+    (polarisations 0 and 3) go through ``cleaners.hogbom`` one at a time, Q and
+    U (1 and 2) together through ``cleaners.hogbom_complex`` as Q + iU.
+
+    :param dirty_list: list of dirty Images [1, 4, ny, nx]
+    :param psf_list: list of PSF Images; Q and U must share one PSF
+    :param window_list: list of window Images, or None
+    :param gain, niter, threshold, fractional_threshold: see ``deconvolve_list``
+    :return: component image list, residual image list (``stokesIQUV``, the
+        dirty image's WCS)
+
+    I or V is skipped when its PSF plane has maximum 0, Q and U when the Q PSF
+    plane has; Q and U are searched under the window of Q, as in the reference.
+    This is called directly: ``deconvolve_list`` does not dispatch to it and
+    applies neither ``psf_support`` nor ``window_shape`` for it, so a caller
+    who wants them runs ``bound_psf_list`` / ``find_window_list`` first.
+
+    Two deviations from the reference: the output planes are written at
+    channel index 0 of every entry (the reference indexes them with the
+    position in the list and raises ``IndexError`` from the second entry on),
+    and an entry whose polarisation axis is not 4 raises ``ValueError`` before
+    any device work.
+    """
+    fracthresh, gain, niter, thresh, _ = common_arguments(**kwargs)
+    for channel, dirty in enumerate(dirty_list):
+        if _pixels(dirty).shape[1] != 4:
+            raise ValueError(f"complex_hogbom_kernel_list: image {channel} has "
+                             f"{_pixels(dirty).shape[1]} polarisations, stokesIQUV needs 4")
+
+    comp_images, residual_images = [], []
+    for channel, dirty in enumerate(dirty_list):
+        pix, psf = _pixels(dirty)[0], _pixels(psf_list[channel])[0]
+        comp_array = _zeros_like(_pixels(dirty))
+        residual_array = _zeros_like(_pixels(dirty))
+        for pol in (0, 3):
+            if float(psf[pol].max()):
+                log.info("complex_hogbom_kernel_list: Processing pol %d, channel %d", pol, channel)
+                comp_array[0, pol], residual_array[0, pol] = hogbom(
+                    pix[pol], psf[pol], _plane(window_list, channel, pol), gain, thresh, niter,
+                    fracthresh)
+            else:
+                log.info("complex_hogbom_kernel_list: Skipping pol %d, channel %d", pol, channel)
+        if float(psf[1].max()):
+            log.info("complex_hogbom_kernel_list: Processing pol 1 and 2, channel %d", channel)
+            (comp_array[0, 1], comp_array[0, 2], residual_array[0, 1],
+             residual_array[0, 2]) = hogbom_complex(
+                pix[1], pix[2], psf[1], psf[2], _plane(window_list, channel, 1), gain, thresh,
+                niter, fracthresh)
+        else:
+            log.info("complex_hogbom_kernel_list: Skipping pol 1 and 2, channel %d", channel)
+        frame, wcs = PolarisationFrame("stokesIQUV"), dirty.image_acc.wcs
+        comp_images.append(Image.constructor(data=comp_array, polarisation_frame=frame, wcs=wcs))
+        residual_images.append(Image.constructor(data=residual_array, polarisation_frame=frame,
+                                                 wcs=wcs))
+    return comp_images, residual_images
 
 
 def mmclean_kernel_list(dirty_list, prefix, psf_list, window_list=None, sensitivity_list=None,

@@ -1203,6 +1203,31 @@ def clean_plane(algorithm, res, psf, comps, gain, pmax, absthresh, niter, window
     return done.value, CLEAN_STOP[reason.value]
 
 
+def clean_plane_complex(res, psf, comps, gain, pmax, absthresh, niter, window=None):
+    """Up to ``niter`` complex Hogbom minor cycles of a Q / U pair cleaned as
+    Q + iU, in place on device f64: ``res`` [2, ny, nx] (plane 0 Q, plane 1 U),
+    ``psf`` [py, px] shared by both, ``comps`` [2, ny, nx]; optional ``window``
+    [ny, nx].  The peak is the first maximum of hypot(q * w, u * w), the
+    component (res[:, peak] * gain) * (1 / pmax), and the cycles stop once
+    hypot(q, u) at the peak is below ``absthresh`` after the subtraction.
+    Returns (cycles run, "niter" | "threshold")."""
+    _on_gpu(res, "res")
+    if res.dim() != 3 or res.shape[0] != 2 or psf.dim() != 2:
+        raise ValueError("res must be [2, ny, nx] and psf [py, px]")
+    _, ny, nx = res.shape
+    pny, pnx = psf.shape
+    _f64_plane(res, "res", (2, ny, nx))
+    _f64_plane(psf, "psf", (pny, pnx))
+    _f64_plane(comps, "comps", (2, ny, nx))
+    if window is not None:
+        _f64_plane(window, "window", (ny, nx))
+    done, reason = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.call("sdp_hip_clean_plane_complex", ny, nx, pny, pnx, _ptr(res), _ptr(psf), _ptr(window),
+              _ptr(comps), float(gain), float(pmax), float(absthresh), int(niter),
+              ctypes.byref(done), ctypes.byref(reason), _stream(res.device))
+    return done.value, CLEAN_STOP[reason.value]
+
+
 # ---- msmfsclean minor cycles (sdp_hip_mfsclean_plane) ----------------------------
 def mfsclean_plane(smresidual, m_model, ssmmpsf, scale_kernels, hsmmpsf, ihsmmpsf, gain, absthresh,
                    niter, findpeak="RASCIL", windowstack=None, sensitivity=None, scale_extent=0):
