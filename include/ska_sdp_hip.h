@@ -1145,6 +1145,64 @@ int sdp_hip_resample_interp(int64_t nrows, int c_in, int c_out, int nrec,
                             const double *x_out, const int32_t *interval,
                             void *stream, char *errbuf, size_t errbuf_len);
 
+/* ---- sums of imaging results and clean thresholds (imaging/imaging_helpers.py)
+ * sdp_hip_sum_planes: one output cube from ncube input cubes of nplane planes
+ * with npix pixels each (reference src/ska_sdp_func_python/imaging/
+ * imaging_helpers.py:25-93).  in_cubes is a HOST array of ncube DEVICE
+ * pointers; every cube is contiguous, plane p of cube n at in_cubes[n] +
+ * p * npix elements; the cubes and out are all f32 or all f64 (dtype).  The
+ * library copies the pointer table to device scratch.  One launch for all
+ * planes; every input is read once and the output written once.  The call
+ * only enqueues work on `stream`.
+ *
+ * weights != NULL (weighted mode): weights [ncube][nplane] and sumwt [nplane]
+ * are DEVICE arrays of doubles that stay allocated until the stream has run.
+ * Every element starts from +0.0 and adds weights[n][p] * (double)in[n][p][i]
+ * in ascending n, the product and the sum each rounded once in fp64.  With
+ * normalise != 0 the element becomes acc / sumwt[p] (a division) where
+ * sumwt[p] > 0 and +0.0 elsewhere, whatever acc is; sumwt may be NULL with
+ * normalise == 0.  An f32 output is rounded once on the store.  For f64 this
+ * is numpy's `im += w[..., None, None] * pixels` over the list followed by
+ * normalise_sumwt, bit for bit.  out overlaps no input.
+ *
+ * weights == NULL (plain mode): acc = in[0], then acc = acc + in[n] for n =
+ * 1 .. ncube - 1 in the element type -- numpy's `a += b`, and exact for
+ * complex data passed as its real view.  out overlaps no input, except that
+ * it may be in_cubes[0] itself.
+ *
+ * 1 <= ncube <= SDP_HIP_SUM_PLANES_MAX, nplane * npix <= 2^40.
+ *
+ * sdp_hip_peak_abs: the largest magnitude in one cube [nchan][npol][ny][nx],
+ * f32 or f64 (dtype), with x contiguous and the distances between rows,
+ * polarisations and channels given in elements (>= 0), so that a sub-image
+ * that is a view of a larger image needs no copy (reference :96-150).
+ *   SDP_HIP_PEAK_MOMENT0  max over pol, y, x of |(sum_c (double)x[c]) / nchan|,
+ *                         the sum from +0.0 in ascending c in fp64, divided
+ *                         by (double)nchan
+ *   SDP_HIP_PEAK_REFCHAN  max over pol, y, x of |x[nchan / 2]|
+ * *peak (HOST) receives the maximum over the values that are not NaN (0 if
+ * there is none), *nan_seen (HOST) 0 or the sum of SDP_HIP_PEAK_NAN_INPUT (an
+ * element read was NaN) and SDP_HIP_PEAK_NAN_MEAN (a channel mean was: inf -
+ * inf included).  The maximum is taken with integer atomics on the bit
+ * pattern of the non-negative doubles: the same on every run.  The call waits
+ * for the stream.  npol * ny * ceil(nx / (16 / sizeof(T))) < 2^31.
+ */
+#define SDP_HIP_SUM_PLANES_MAX 4096
+#define SDP_HIP_PEAK_MOMENT0 0
+#define SDP_HIP_PEAK_REFCHAN 1
+#define SDP_HIP_PEAK_NAN_INPUT 1
+#define SDP_HIP_PEAK_NAN_MEAN 2
+int sdp_hip_sum_planes(int ncube, int64_t nplane, int64_t npix,
+                       const void *const *in_cubes, int dtype, void *out,
+                       const double *weights, const double *sumwt,
+                       int normalise, void *stream, char *errbuf,
+                       size_t errbuf_len);
+int sdp_hip_peak_abs(int mode, int nchan, int npol, int ny, int nx,
+                     const void *cube, int dtype, int64_t chan_stride,
+                     int64_t pol_stride, int64_t row_stride, double *peak,
+                     int *nan_seen, void *stream, char *errbuf,
+                     size_t errbuf_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,11 @@ SDP_HIP_GAIN_CHAIN_MAX = 8
 SDP_HIP_GAUSS_FIT_WINDOW = 15
 SDP_HIP_BANDPASS_MAX_DEGREE = 7
 SDP_HIP_BANDPASS_MAX_SEGMENTS = 64
+SDP_HIP_SUM_PLANES_MAX = 4096
+SDP_HIP_PEAK_MOMENT0 = 0
+SDP_HIP_PEAK_REFCHAN = 1
+SDP_HIP_PEAK_NAN_INPUT = 1
+SDP_HIP_PEAK_NAN_MEAN = 2
 
 c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
@@ -286,6 +291,13 @@ SIGNATURES = {
     "sdp_hip_resample_interp": [
         c_i64, c_int, c_int, c_int,               # nrows, c_in, c_out, nrec
         c_vp, c_vp, c_vp, c_vp, c_vp, c_vp] + _ERR,  # gain, out, x_in, x_out, interval, stream
+    "sdp_hip_sum_planes": [
+        c_int, c_i64, c_i64, c_vp, c_int, c_vp,   # ncube, nplane, npix, in_cubes (host), dtype, out
+        c_vp, c_vp, c_int, c_vp] + _ERR,          # weights, sumwt (device), normalise, stream
+    "sdp_hip_peak_abs": [
+        c_int, c_int, c_int, c_int, c_int,        # mode, nchan, npol, ny, nx
+        c_vp, c_int, c_i64, c_i64, c_i64,         # cube, dtype, chan / pol / row strides
+        ctypes.POINTER(c_dbl), ctypes.POINTER(c_int), c_vp] + _ERR,  # peak, nan_seen (host), stream
 }
 
 _lock = threading.Lock()

@@ -794,11 +794,15 @@ class _GTAcc:
 
 
 class Configuration:
-    """The array configuration as far as gain tables read it: its ``name``
-    ("LOW-AA0.5", "MID", ...)."""
+    """The array configuration as far as gain tables and advise_wide_field
+    read it: its ``name`` ("LOW-AA0.5", "MID", ...) and, optionally, the
+    station or dish ``diameter`` in metres (a scalar or one value per
+    antenna), read as ``configuration.diameter.data``."""
 
-    def __init__(self, name=""):
+    def __init__(self, name="", diameter=None):
         self.name = name
+        if diameter is not None:
+            self.diameter = _Plain(np.asarray(diameter, dtype=float))
 
     def __repr__(self):
         return f"Configuration('{self.name}')"
