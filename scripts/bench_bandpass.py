@@ -118,14 +118,14 @@ def main():
             tabs = [torch.as_tensor(a, device=dev) for a in (q, e, seg, ed)]
             call = lambda: _lib.call(  # noqa: E731
                 "sdp_hip_resample_polyfit", nt * na, c_in, c_out, 2, deg, len(ed) - 1,
-                kernels._ptr(gain), kernels._ptr(out), *[kernels._ptr(t) for t in tabs],
-                kernels._stream(dev))
+                kernels.ptr(gain), kernels.ptr(out), *[kernels.ptr(t) for t in tabs],
+                kernels.stream(dev))
         else:
             tabs = [torch.as_tensor(a, device=dev)
                     for a in (f_in, f_out, bu.interp_intervals(f_out, f_in))]
             call = lambda: _lib.call(  # noqa: E731
-                "sdp_hip_resample_interp", nt * na, c_in, c_out, 2, kernels._ptr(gain),
-                kernels._ptr(out), *[kernels._ptr(t) for t in tabs], kernels._stream(dev))
+                "sdp_hip_resample_interp", nt * na, c_in, c_out, 2, kernels.ptr(gain),
+                kernels.ptr(out), *[kernels.ptr(t) for t in tabs], kernels.stream(dev))
         k_ms, _, _, k_range = event_ms(call, args.warmup, args.repeats)
         kw = dict(edges=edges, polydeg=deg) if alg == "polyfit" else {}
         w_dev, w_host, whole, w_range = event_ms(

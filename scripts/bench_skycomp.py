@@ -85,7 +85,7 @@ def measure(fn, warmup, repeats):
 
 def tile_traffic(boxes, ncomp, ny, nx, nplanes):
     """Image bytes read plus written by a tiled kernel, and its (tile, component) pairs."""
-    ptr, comp = kernels._tile_csr(boxes, 0, ncomp, ny, nx, torch.device("cuda:0"))
+    ptr, comp = kernels.tile_csr(boxes, 0, ncomp, ny, nx, torch.device("cuda:0"))
     tiles = int(torch.count_nonzero(torch.diff(ptr)))
     pixels = tiles * _lib.SDP_HIP_SKYCOMP_TILE_X * _lib.SDP_HIP_SKYCOMP_TILE_Y
     return 2 * 8 * nplanes * pixels, int(comp.numel())
@@ -126,7 +126,7 @@ def main():
     image.zero_()
     kernels.skycomp_insert(image, origin, ty, tx, isum, flux)
     equal = bool(np.array_equal(image.cpu().numpy(), host))
-    boxes = kernels._tile_boxes(origin[:, 0], origin[:, 0] + 2 * S - 1, origin[:, 1],
+    boxes = kernels.tile_boxes(origin[:, 0], origin[:, 0] + 2 * S - 1, origin[:, 1],
                                 origin[:, 1] + 2 * S - 1, n, n)
     moved, pairs = tile_traffic(boxes, ncomp, n, n, npol)
     print(json.dumps({"op": "insert", "npix": n, "ncomp": ncomp, "method": "Lanczos", "support": S,
@@ -150,7 +150,7 @@ def main():
     numpy_ms = 1e3 * (time.perf_counter() - t0) * ncomp / nref
     err = float(np.abs(image.cpu().numpy() - host).max() / np.abs(flux[:nref]).sum(axis=0).max())
     r = np.sqrt(kernels.RESTORE_SKIP_ARGUMENT / (a * (1.0 - 1e-9))) + 1.0
-    boxes = kernels._tile_boxes(np.floor(xy[:, 0] - r), np.ceil(xy[:, 0] + r),
+    boxes = kernels.tile_boxes(np.floor(xy[:, 0] - r), np.ceil(xy[:, 0] + r),
                                 np.floor(xy[:, 1] - r), np.ceil(xy[:, 1] + r), n, n)
     moved, pairs = tile_traffic(boxes, ncomp, n, n, npol)
     print(json.dumps({"op": "restore", "npix": n, "ncomp": ncomp, "fwhm_pixels": args.fwhm,

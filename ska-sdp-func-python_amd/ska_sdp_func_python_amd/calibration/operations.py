@@ -71,7 +71,7 @@ def apply_gaintable(vis, gt, inverse=False, use_flags=False):
     fl = None
     if use_flags:
         fl = _device.to_dev(vis["flags"].data, None, dev)
-        if fl.dtype not in kernels._FLAG_DT:
+        if fl.dtype not in kernels.FLAG_BYTES:
             fl = fl.to(torch.int64)
         fl = fl.contiguous()
     bl = np.asarray(vis.baselines.data)

@@ -92,7 +92,7 @@ def solve_gaintable(vis, modelvis=None, gain_table=None, phase_only=True, niter=
         m = _device.to_dev(modelvis["vis"].data, v.dtype, dev).contiguous()
     w = _device.to_dev(vis["weight"].data, torch.float64, dev).contiguous()
     fl = _device.to_dev(vis["flags"].data, None, dev)
-    if fl.dtype not in kernels._FLAG_DT:
+    if fl.dtype not in kernels.FLAG_BYTES:
         fl = fl.to(torch.int64)
     ptr, tidx, present = _windows(np.asarray(vis.time.data, dtype=float), gain_table)
     for row in np.nonzero(~present)[0]:

@@ -162,7 +162,7 @@ def _weight_inputs(vis, dev):
     freq = _device.to_dev(np.asarray(vis.frequency.data, dtype=float), torch.float64, dev)
     wt = _device.to_dev(vis.weight.data, torch.float64, dev).reshape(nrow, nvchan, nvpol).contiguous()
     fl = _device.to_dev(vis.flags.data, None, dev)
-    if fl.dtype not in kernels._FLAG_BYTES:
+    if fl.dtype not in kernels.FLAG_BYTES:
         fl = fl.to(torch.int64)
     fl = fl.reshape(nrow, nvchan, nvpol).contiguous()
     return uvw, freq, wt, fl

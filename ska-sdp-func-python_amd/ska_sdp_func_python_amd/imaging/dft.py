@@ -73,7 +73,7 @@ def idft_visibility_skycomponent(vis, sc):
     if v.dtype not in (torch.complex64, torch.complex128):
         v = v.to(torch.complex128)
     flags = _device.to_dev(vis["flags"].data, None, dev)
-    if flags.dtype not in kernels._FLAG_DT:
+    if flags.dtype not in kernels.FLAG_BYTES:
         flags = flags.to(torch.int64)
     uvw = _device.to_dev(vis.uvw.data, torch.float64, dev).reshape(nt * nb, 3)
     freq = _device.to_dev(np.asarray(vis.frequency.data, float), torch.float64, dev)

@@ -324,7 +324,7 @@ def invert_ng(bvis, model, dopsf=False, normalise=True, **kwargs):
                                  nrow * vnchan, max_call)
 
     def typed(flags, wgt, ms):
-        if flags.dtype not in kernels._FLAG_DT:
+        if flags.dtype not in kernels.FLAG_BYTES:
             flags = flags.to(torch.int64)
         if wgt.dtype not in (torch.float32, torch.float64):
             wgt = wgt.to(torch.float64)

@@ -93,7 +93,7 @@ def _operands(vis, imaging_weight=True):
     if imaging_weight:
         iw = _device.to_dev(vis["imaging_weight"].data, torch.float64, dev).contiguous()
     fl = _device.to_dev(vis["flags"].data, None, dev)
-    if fl.dtype not in kernels._FLAG_DT:
+    if fl.dtype not in kernels.FLAG_BYTES:
         fl = fl.to(torch.int64)
     return v.contiguous(), w, iw, fl.contiguous()
 
@@ -351,7 +351,7 @@ def divide_visibility(vis, modelvis):
     m = _device.to_dev(modelvis["vis"].data, v.dtype, dev).contiguous()
     w = _device.to_dev(vis["weight"].data, torch.float64, dev).contiguous()
     fl = _device.to_dev(vis["flags"].data, None, dev)
-    if fl.dtype not in kernels._FLAG_DT:
+    if fl.dtype not in kernels.FLAG_BYTES:
         fl = fl.to(torch.int64)
     mfl = None
     if modelvis["flags"].data is not vis["flags"].data:

@@ -242,7 +242,7 @@ def test_gather_facets_refuses_bad_arguments():
         host = [ctypes.c_void_p(0) if a is None else ctypes.c_void_p(a.ctypes.data)
                 for a in tuple(tabs) + tuple(tapers)]
         _lib.call("sdp_hip_gather_facets", dtype, facets, nplanes, *size, *facet, *origin, *step,
-                  *host, 0, *[kernels._ptr(o) for o in outputs], kernels._stream(_dev()))
+                  *host, 0, *[kernels.ptr(o) for o in outputs], kernels.stream(_dev()))
 
     with pytest.raises(ValueError, match="1 .. 256 facets"):
         call(facets=many)

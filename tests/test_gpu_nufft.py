@@ -1163,13 +1163,13 @@ def test_two_slots_on_two_streams_overlap_correctly():
     with pytest.raises(ValueError, match="SLOT1"):
         bbuf = (ctypes.c_double * 6)(*b)
         info = kernels._lib.WGridInfo()
-        kernels._lib.call("sdp_hip_ms2dirty_batch", kernels._ptr(U), U.stride(0), kernels._ptr(F),
-                          F.shape[0], U.shape[0], kernels._ptr(M), kernels._lib.SDP_HIP_C64,
+        kernels._lib.call("sdp_hip_ms2dirty_batch", kernels.ptr(U), U.stride(0), kernels.ptr(F),
+                          F.shape[0], U.shape[0], kernels.ptr(M), kernels._lib.SDP_HIP_C64,
                           M.stride(0), M.stride(1), None, kernels._lib.SDP_HIP_F32, 0, 0, 256, 256,
                           cell, cell, 1e-7, 1,
                           kernels._lib.SDP_HIP_SLOT1 | kernels._lib.SDP_HIP_BATCH_FIRST,
                           ctypes.cast(bbuf, ctypes.c_void_p), None, 0, 0,
-                          kernels._stream(dev), ctypes.byref(info))
+                          kernels.stream(dev), ctypes.byref(info))
 
 
 def test_invert_after_workspace_release_is_unchanged():

@@ -89,7 +89,7 @@ def test_insert_adds_in_component_order(max_pairs, monkeypatch):
     from ska_sdp_func_python_amd import kernels
     from ska_sdp_func_python_amd.sky_component import insert_skycomponent
     if max_pairs:
-        monkeypatch.setattr(kernels, "SKYCOMP_MAX_PAIRS", max_pairs)
+        monkeypatch.setattr(kernels.skycomp, "SKYCOMP_MAX_PAIRS", max_pairs)
     rng = np.random.default_rng(11)
     geometry = R.geometry(1, "stokesIQUV")
     pos = np.array([(20.3, 30.7), (23.6, 33.4), (40.45, 47.55)])[np.arange(300) % 3]

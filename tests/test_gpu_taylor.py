@@ -186,7 +186,7 @@ def test_mix_planes_refuses_bad_arguments():
     def call(nin, nout, npix, in_tab, dtype=_lib.SDP_HIP_F64):
         _lib.call("sdp_hip_mix_planes", nin, nout, npix, ctypes.cast(in_tab, ctypes.c_void_p),
                   dtype, ctypes.cast(otab, ctypes.c_void_p), ctypes.c_void_p(wts.ctypes.data),
-                  ctypes.POINTER(ctypes.c_int)(), kernels._stream(_dev()))
+                  ctypes.POINTER(ctypes.c_int)(), kernels.stream(_dev()))
 
     with pytest.raises(ValueError, match="at most 4096"):
         call(many, 1, 221, tab)

@@ -177,15 +177,15 @@ def test_epsilon_below_fp32_floor_is_reported_once(caplog):
     import logging
     import torch
     from ska_sdp_func_python_amd import _lib, kernels
-    kernels._eps_warned = False
-    assert kernels._prec_bits(1e-12) == 0 and kernels._prec_bits(1e-6, "fp32") == 0
+    kernels.wgrid._eps_warned = False
+    assert kernels.wgrid._prec_bits(1e-12) == 0 and kernels.wgrid._prec_bits(1e-6, "fp32") == 0
     with caplog.at_level(logging.WARNING, logger="func-python-logger"):
         for _ in range(2):
-            assert kernels._prec_bits(1e-12, "fp32") == _lib.SDP_HIP_FP32
+            assert kernels.wgrid._prec_bits(1e-12, "fp32") == _lib.SDP_HIP_FP32
     msgs = [r.getMessage() for r in caplog.records if "floor epsilon" in r.getMessage()]
     assert len(msgs) == 1 and "1.0e-12" in msgs[0]
     with pytest.raises(ValueError):
-        kernels._prec_bits(1e-12, "fp16")
+        kernels.wgrid._prec_bits(1e-12, "fp16")
     uvw = torch.zeros((4, 3), dtype=torch.float64)
     with pytest.raises(ValueError):  # host tensors are rejected
         kernels.ms2dirty(uvw, torch.ones(1), None, None, 8, 8, 1e-3, 1e-3, 1e-12,

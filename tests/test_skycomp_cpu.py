@@ -220,7 +220,7 @@ def test_voronoi_iter_with_one_component_is_all_ones(host_layer):
 # ---- 4. the per-tile component lists ------------------------------------------
 def _lists(boxes, start, stop, ny, nx):
     from ska_sdp_func_python_amd import kernels
-    ptr, comp = (t.numpy() for t in kernels._tile_csr(boxes, start, stop, ny, nx, torch.device("cpu")))
+    ptr, comp = (t.numpy() for t in kernels.tile_csr(boxes, start, stop, ny, nx, torch.device("cpu")))
     assert ptr.dtype == np.int64 and comp.dtype == np.int32 and ptr[0] == 0 and ptr[-1] == len(comp)
     return [comp[ptr[t]:ptr[t + 1]] for t in range(len(ptr) - 1)]
 
@@ -232,7 +232,7 @@ def test_tile_lists_hold_every_overlapping_component_in_order():
     ny, nx, n = R.NY, R.NX, 200
     x_lo, y_lo = rng.integers(-40, nx + 20, n), rng.integers(-40, ny + 20, n)
     x_hi, y_hi = x_lo + rng.integers(0, 40, n), y_lo + rng.integers(0, 40, n)
-    boxes = kernels._tile_boxes(x_lo, x_hi, y_lo, y_hi, ny, nx)
+    boxes = kernels.tile_boxes(x_lo, x_hi, y_lo, y_hi, ny, nx)
     lists = _lists(boxes, 0, n, ny, nx)
     tiles_x = -(-nx // tx)
     assert len(lists) == tiles_x * -(-ny // ty)
@@ -249,9 +249,9 @@ def test_launches_split_the_components_in_order(monkeypatch):
     rng = np.random.default_rng(6)
     n = 50
     x_lo, y_lo = rng.integers(0, R.NX, n), rng.integers(0, R.NY, n)
-    boxes = kernels._tile_boxes(x_lo, x_lo + 20, y_lo, y_lo + 20, R.NY, R.NX)
-    monkeypatch.setattr(kernels, "SKYCOMP_MAX_PAIRS", 25)
-    ranges = list(kernels._skycomp_launches(boxes, n))
+    boxes = kernels.tile_boxes(x_lo, x_lo + 20, y_lo, y_lo + 20, R.NY, R.NX)
+    monkeypatch.setattr(kernels.skycomp, "SKYCOMP_MAX_PAIRS", 25)
+    ranges = list(kernels.skycomp._skycomp_launches(boxes, n))
     assert len(ranges) > 3 and ranges[0][0] == 0 and ranges[-1][1] == n
     assert all(a[1] == b[0] for a, b in zip(ranges, ranges[1:]))
     for s, e in ranges:
@@ -272,9 +272,9 @@ def test_restore_leaves_out_only_what_underflows(monkeypatch):
     a, b, c = _gaussian_coefficients(0.5, 1.1, np.deg2rad(-60.0))
     xy = np.array([(20.3, 30.7), (-10.4, 40.3), (60.2, 82.9), (-200.0, 30.0)])
     seen = {}
-    monkeypatch.setattr(kernels, "_skycomp_image", lambda image: (1, R.NY, R.NX))
-    monkeypatch.setattr(kernels, "_ptr", lambda v: v)
-    monkeypatch.setattr(kernels, "_stream", lambda dev: None)
+    monkeypatch.setattr(kernels.skycomp, "_skycomp_image", lambda image: (1, R.NY, R.NX))
+    monkeypatch.setattr(kernels.skycomp, "ptr", lambda v: v)
+    monkeypatch.setattr(kernels.skycomp, "stream", lambda dev: None)
     monkeypatch.setattr(_lib, "call", lambda name, *args: seen.update(ptr=args[11].numpy(),
                                                                      comp=args[12].numpy()))
     image = torch.zeros((1, 1, R.NY, R.NX), dtype=torch.float64)
