@@ -1203,6 +1203,45 @@ int sdp_hip_peak_abs(int mode, int nchan, int npol, int ny, int nx,
                      int *nan_seen, void *stream, char *errbuf,
                      size_t errbuf_len);
 
+/* ---- oversampled w-projection kernels (grid_data/convolution_functions.py)
+ * sdp_hip_wkernel_create: the convolution functions of nw w planes, sampled
+ * from the centred inverse FFT of a far field of npixel x npixel pixels padded
+ * to npad = oversampling * npixel, without ever forming the padded plane.
+ * With os = oversampling, h = os / 2, nd = 2 h + 1 and c = npixel / 2, plane
+ * (b, z) of the result is
+ *   cf[b][z][iv][iu][kv][ku] = (1 / npixel^2) sum_y sum_x
+ *        e(jv, y) * a[b][z][y][x] * e(ju, x)
+ *   jv = os * (kv - support / 2) - (iv - h),  ju likewise from ku and iu
+ *   e(j, x) = exp(+2 pi i ((j * (x - c)) mod npad) / npad)
+ * which is os * os times element [npad / 2 + jv][npad / 2 + ju] of that
+ * inverse FFT.  The far field is
+ *   a[b][z][y][x] = beam(w[z], y, x) * (taper[y] * taper[x]) * pb[b][y][x]
+ *   r2 = fov * fov * (((y - c) / npixel)^2 + ((x - c) / npixel)^2)
+ *   beam = exp(i * ((-2 pi) * -w[z]) * (1 - sqrt(1 - r2))),
+ *          0 where r2 >= 1, 1 where r2 == 0
+ * in fp64 with every operation rounded once (the expression of the
+ * reference's w_beam for -w[z], cancellation in 1 - sqrt(1 - r2) included).
+ * taper == NULL and pb == NULL stand for ones; with pb == NULL npb is 1.
+ *
+ * w [nw] and taper [npixel] are DEVICE doubles, pb [npb][npixel][npixel] and
+ * cf [npb][nw][nd][nd][support][support] DEVICE complex128, all contiguous.
+ * The exponent of e() is reduced as an integer before sincospi, so every
+ * twiddle is accurate to an ulp whatever npad is.  The sums run as two complex
+ * matrix products per plane in plain fp64 FMAs, x first, each sum in
+ * ascending index from +0: no atomics, and the bits of a plane depend on
+ * nothing but w[z], pb[b] and the geometry -- not on nw, on the other planes
+ * of the call or on how the library chunks them.  Samples with equal (jv, ju)
+ * have equal bits: for an even os, [iu = 2 h][ku] equals [iu = 0][ku - 1].
+ * The call only enqueues work on `stream`; scratch is the library's.
+ *
+ * npixel even, support + 2 <= npixel <= 4096; support even, >= 2; os >= 1;
+ * nd * support <= 32768; nw, npb >= 1; npb * nw < 2^31.
+ */
+int sdp_hip_wkernel_create(int npixel, int oversampling, int support, int nw,
+                           int npb, double field_of_view, const double *w,
+                           const double *taper, const void *pb, void *cf,
+                           void *stream, char *errbuf, size_t errbuf_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -298,6 +298,9 @@ SIGNATURES = {
         c_int, c_int, c_int, c_int, c_int,        # mode, nchan, npol, ny, nx
         c_vp, c_int, c_i64, c_i64, c_i64,         # cube, dtype, chan / pol / row strides
         ctypes.POINTER(c_dbl), ctypes.POINTER(c_int), c_vp] + _ERR,  # peak, nan_seen (host), stream
+    "sdp_hip_wkernel_create": [
+        c_int, c_int, c_int, c_int, c_int, c_dbl,  # npixel, oversampling, support, nw, npb, fov
+        c_vp, c_vp, c_vp, c_vp, c_vp] + _ERR,     # w, taper, pb, cf, stream
 }
 
 _lock = threading.Lock()

@@ -37,3 +37,4 @@ from .segment import SEGMENT_KERNEL_MAX, segment_image, segment_peaks  # noqa: F
 from .gaussfit import GAUSS_FIT_STATUS, GAUSS_FIT_WINDOW, gauss_fit  # noqa: F401
 from .bandpass import (BANDPASS_MAX_DEGREE, BANDPASS_MAX_SEGMENTS, resample_interp,  # noqa: F401
                        resample_polyfit)
+from .wkernel import wkernel_create  # noqa: F401
